@@ -2,8 +2,18 @@
 """Headline benchmark: reenacted frames/s at 256x256 (BASELINE.json), MI355X-native generator path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config synthesis|inference|trainer] [--batch B] [--cm 1]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs)
+and the line.  Everything else it can measure or check -- the other timed legs of a config, the conv roofline pass, the sustained
+leg, the other arithmetics, configs and shapes, max_abs_vs_oracle and the CPU baseline -- runs with --full only; the --no-* and
+--layers switches below act on a --full run.
+
+--dump-outputs DIR writes what the timed path returned from its LAST timed step (rank 0) as float32 DIR/<name>.npy: synthesis
+`images`, inference `frames`, trainer `images` + `loss`, pti `loss`.  Inputs are seeded, so two builds run with the same
+arguments can be compared file by file; past DUMP_BYTES in all, every array is cut to the same seeded sample of its elements.
 
 `--gpus N` with N > 1 and no torchrun environment starts the N ranks ITSELF (re-executes under torch.distributed.run on
 127.0.0.1, one process per GPU, backend nccl = RCCL); it refuses to run when fewer than N devices are visible, and every
@@ -100,6 +110,11 @@ def parse_args(argv=None):
     ap.add_argument('--host-check', action='store_true',
                     help='run only the multi-rank host flow (launch, process group, weight broadcast, sharding) on CPU '
                          'tensors over gloo and print what each rank saw -- no generator launch, no GPU needed')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beside the headline figure (other timed legs, roofline pass, sustained leg, other '
+                         'arithmetics / configs / shapes, oracle check, CPU baseline); a plain run times the headline steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as float32 DIR/<name>.npy (rank 0)')
     args = ap.parse_args(argv)
     if args.batch is None:
         args.batch = DEFAULT_BATCH[args.config]
@@ -157,8 +172,7 @@ def host_check(args, rank, world):
                      'weight_broadcast_bytes': nbytes, 'broadcast_ms': round(t_b * 1e3, 2),
                      'shards': [[int(s[1]), int(s[2])] for s in seen], 'rank_affinity': AFFINITY,
                      'weights_identical_on_all_ranks': all(x == sums[0] for x in sums),
-                     'roofline': {'bound': 'mfma', 'achieved': None, 'peak': round(FP32_MFMA_PEAK_TFLOPS if args.precision == 'fp32' else SPLIT_PEAK_TFLOPS, 1), 'unit': 'TFLOP/s', 'frac': None,
-                                  'traffic': None, 'reason': why},
+                     'roofline': unmeasured_roofline(args.precision, why),
                      'max_abs_vs_oracle': {'last_rank_shard': None, 'reason': why}})
         emit(line, args, world)
 
@@ -217,7 +231,8 @@ def attach_pmc(roof, t):
 
 
 def timed_region(step, args, dev, finish=None):
-    """W warm-up steps, then EXACTLY K steps between (barrier + synchronize) pairs; returns (max over ranks, this rank).
+    """W warm-up steps, then EXACTLY K steps between (barrier + synchronize) pairs; returns (max over ranks, this rank, what the
+    K-th step returned).
     finish: called after the K-th step inside the timed region (a pipelined step checks the PREVIOUS step's result: the last
     step's own check belongs to the K steps too)."""
     import gc
@@ -233,7 +248,7 @@ def timed_region(step, args, dev, finish=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            out = step()
         if finish is not None:
             finish()
         torch.cuda.synchronize()
@@ -244,6 +259,33 @@ def timed_region(step, args, dev, finish=None):
         if gc_was:
             gc.enable()
     return D.max_over_ranks(elapsed, dev), mine, out
+
+
+DUMP_BYTES = 60 * 10 ** 6          # all --dump-outputs arrays together (the .npy headers stay inside 64 MB)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: {name: tensor} -> float32 DIR/<name>.npy (integer outputs convert exactly).  Arrays are written whole while
+    they fit DUMP_BYTES together; past it, each keeps its share of DUMP_BYTES as a fixed seeded sample of its flattened elements (the
+    same positions in every run), so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(SEED).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
+def unmeasured_roofline(precision, reason):
+    """The roofline object of a line whose conv launches were not timed (plain run, host check): the contract keys, null figures."""
+    return {'bound': 'mfma', 'achieved': None, 'peak': round(FP32_MFMA_PEAK_TFLOPS if precision == 'fp32' else SPLIT_PEAK_TFLOPS, 1),
+            'unit': 'TFLOP/s', 'frac': None, 'traffic': None, 'reason': reason}
+
+
+NOT_FULL = 'measured by bench.py --full only'
 
 
 def conv_roofline(step, steps, peak, kernel_desc, units_per_step):
@@ -561,11 +603,12 @@ def finalize_line(out, args, world):
         out['cpu_baseline'] = {'value': None, 'unit': out.get('unit'), 'cores': None, 'kind': 'port', 'sample': None,
                                'reason': ('the CPU baseline is timed on rank 0 at N=1 only (the N=1 line of the same commit carries it): '
                                           'with %d ranks the host cores are divided between the ranks' % world) if world > 1
+                               else NOT_FULL if not args.full
                                else ('--no-cpu-baseline' if args.no_cpu_baseline else 'this --config times it in the synthesis line only')}
     missing = [k for k in CONTRACT_KEYS if k not in out]
     roof = out.get('roofline') or {}
     missing += ['roofline.' + k for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic') if k not in roof]
-    if world > 1 and args.config == 'synthesis' and not args.no_oracle_delta and not args.host_check:
+    if world > 1 and args.config == 'synthesis' and args.full and not args.no_oracle_delta and not args.host_check:
         if 'last_rank_shard' not in (out.get('max_abs_vs_oracle') or {}):
             missing.append('max_abs_vs_oracle.last_rank_shard')
     if out.get('n_gpus') != world:
@@ -785,31 +828,37 @@ def run_synthesis(args, rank, world, dev):
     F_.set_precision(args.precision)
     sustained = single = unverified = default_call = fallback = None
     with torch.no_grad():
-        if pipe is not None:
+        if pipe is not None and args.full:
             e1, _, _ = timed_region(step1, args, dev)
             single = {'value': round(B * world * args.steps / e1, 2), 'unit': 'frames/s', 'ms_per_step': round(e1 / args.steps * 1e3, 3),
                       'what': 'unverified forwards back to back on one HIP stream'}
-        eu, _, _ = timed_region(step_unverified, args, dev)
-        unverified = {'value': round(B * world * args.steps / eu, 2), 'unit': 'frames/s', 'ms_per_step': round(eu / args.steps * 1e3, 3),
-                      'what': 'verify_range=False and nobody checks the tokens (round 3\'s `value`)'}
-        ed, _, _ = timed_region(step_default, args, dev)
-        default_call = {'value': round(B * world * args.steps / ed, 2), 'unit': 'frames/s', 'ms_per_step': round(ed / args.steps * 1e3, 3),
-                        'what': 'G([w], input_is_latent=True) as the reference scripts call it: each call waits for its own batch and '
-                                'returns verified frames (one stream, hipGraph replay)'}
+        if args.full:
+            eu, _, _ = timed_region(step_unverified, args, dev)
+            unverified = {'value': round(B * world * args.steps / eu, 2), 'unit': 'frames/s', 'ms_per_step': round(eu / args.steps * 1e3, 3),
+                          'what': 'verify_range=False and nobody checks the tokens (round 3\'s `value`)'}
+            ed, _, _ = timed_region(step_default, args, dev)
+            default_call = {'value': round(B * world * args.steps / ed, 2), 'unit': 'frames/s', 'ms_per_step': round(ed / args.steps * 1e3, 3),
+                            'what': 'G([w], input_is_latent=True) as the reference scripts call it: each call waits for its own batch and '
+                                    'returns verified frames (one stream, hipGraph replay)'}
         elapsed, mine, img = timed_region(step, args, dev, finish=finish)
         assert img.shape == (hi - lo, 3, args.size, args.size) and bool(torch.isfinite(img).all())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'images': img})
         head = {args.precision: img[:2].clone()}            # rows 0, 1 of the timed batch -> max_abs_vs_oracle
         spread = rank_spread((hi - lo) * args.steps, mine, dev, world)
-        if args.sustain > 0:
+        if args.sustain > 0 and args.full:
             n_s, wall_s, sustained = sustained_leg(step, B, elapsed / args.steps * 1e3, dev, args.sustain,
                                                    join=pipe.join if pipe is not None else None)
             finish()
             sustained['frames_per_s'] = round(B * world * n_s / wall_s, 2)
-        roof = roofline_for(args.precision, step1, args.steps, B)
-        attach_pmc(roof, pmc_traffic(args, B))
+        if args.full:
+            roof = roofline_for(args.precision, step1, args.steps, B)
+            attach_pmc(roof, pmc_traffic(args, B))
+        else:
+            roof = unmeasured_roofline(args.precision, NOT_FULL)
         alt = None
         alt_mode = 'fp32' if args.precision != 'fp32' else 'fp16x3'
-        if not args.no_alt:
+        if not args.no_alt and args.full:
             exact = step1()
             F_.set_precision(alt_mode)
             try:
@@ -834,7 +883,7 @@ def run_synthesis(args, rank, world, dev):
                             'max_abs_vs_default_arithmetic': float((fb - exact).abs().max())}
     # the oracle check on a shard that is NOT rank 0's: the last rank runs it on its first two rows (own range plan, own latents)
     far = None
-    if world > 1 and not args.no_oracle_delta:
+    if world > 1 and args.full and not args.no_oracle_delta:
         mine_delta = oracle_delta(args.size, args.cm, w[:2], {args.precision: head[args.precision]}) if rank == world - 1 else None
         far = D.gather_objects(mine_delta)[world - 1]
     if rank != 0:
@@ -860,7 +909,7 @@ def run_synthesis(args, rank, world, dev):
                                  'clocks to its power budget, quote the sustained figure for long runs'
                                  % ((sustained['vs_value'] - 1) * 100))
         out['sustained'] = sustained
-    if not args.no_oracle_delta and w.shape[0] >= 2:
+    if args.full and not args.no_oracle_delta and w.shape[0] >= 2:
         # the second half of BASELINE.json's metric: max-abs delta vs the reference (through its pinned restatement) on the
         # same latents as the timed batch
         out['max_abs_vs_oracle'] = oracle_delta(args.size, args.cm, w[:2], head)
@@ -868,10 +917,11 @@ def run_synthesis(args, rank, world, dev):
             out['max_abs_vs_oracle']['last_rank_shard'] = far
     # end to end: ALL algorithmic FLOPs of a step (the 3x3 convs are 98.8 % of the path) over the timed step, the
     # figure the driver can recompute from `ms_per_step`; `frac` above is the conv launches alone
-    step_flops = roof['alg_gflop_per_unit'] * 1e9 * B
-    roof['end_to_end'] = {'achieved': round(step_flops / (elapsed / args.steps) / 1e12, 2), 'unit': 'TFLOP/s',
-                          'frac': round(step_flops / (elapsed / args.steps) / 1e12 / roof['peak'], 4),
-                          'what': 'conv FLOPs of a step / ms_per_step of `value` / peak (everything that is not a conv launch counts as lost time)'}
+    if args.full:
+        step_flops = roof['alg_gflop_per_unit'] * 1e9 * B
+        roof['end_to_end'] = {'achieved': round(step_flops / (elapsed / args.steps) / 1e12, 2), 'unit': 'TFLOP/s',
+                              'frac': round(step_flops / (elapsed / args.steps) / 1e12 / roof['peak'], 4),
+                              'what': 'conv FLOPs of a step / ms_per_step of `value` / peak (everything that is not a conv launch counts as lost time)'}
     if single is not None:
         roof['end_to_end']['single_stream_frac'] = round(step_flops / (single['ms_per_step'] * 1e-3) / 1e12 / roof['peak'], 4)
     out['roofline'] = roof
@@ -886,16 +936,16 @@ def run_synthesis(args, rank, world, dev):
         if 'max_abs_vs_oracle' in out:
             fallback['max_abs_vs_oracle'] = out['max_abs_vs_oracle'].get('bf16x3')
         out['fallback_arithmetic'] = fallback
-    if args.layers:
+    if args.layers and args.full:
         for e in roof['per_layer']:
             sys.stderr.write('%-34s %8.1f us/launch %7.1f TFLOP/s  %.3f\n' % (e['layer'], e['us'], e['tflops'], e['frac']))
         for e in roof['hbm_bound']:
             sys.stderr.write('%-44s %8.1f us/launch %7.1f GB/s  %.3f\n' % (e['launch'], e['us'], e['gbs'], e['frac']))
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and args.full and not args.no_other_configs:
         del G, w, img
         torch.cuda.empty_cache()
         out['other_configs'] = other_config_legs(args, rank, world, dev)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(args.size, args.cm)
     return out
 
@@ -909,6 +959,7 @@ def other_config_legs(args, rank, world, dev):
         # the same synthesis-only workload -- frames/s, every conv row, max-abs vs the oracle on the timed batch
         sub = argparse.Namespace(**vars(args))
         sub.cm, sub.no_alt, sub.sustain, sub.no_other_configs, sub.no_cpu_baseline, sub.layers = 2, True, 0, True, True, False
+        sub.dump_outputs = None                    # (the headline step's outputs only)
         sub.steps, sub.warmup = max(5, min(args.steps, 20)), max(3, min(args.warmup, 5))
         t0 = time.perf_counter()
         try:
@@ -932,6 +983,7 @@ def other_config_legs(args, rank, world, dev):
         # on its own timed batch against the same oracle and the same 1e-3 bar.
         sub = argparse.Namespace(**vars(args))
         sub.no_alt, sub.sustain, sub.no_other_configs, sub.no_cpu_baseline, sub.layers = True, 0, True, True, False
+        sub.dump_outputs = None
         sub.steps, sub.warmup = max(5, min(args.steps, 20)), max(3, min(args.warmup, 5))
         t0 = time.perf_counter()
         base_cfg = F_.config()
@@ -964,6 +1016,7 @@ def other_config_legs(args, rank, world, dev):
         sub = argparse.Namespace(**vars(args))
         sub.config, sub.batch = name, DEFAULT_BATCH[name]
         sub.skip_e4e_batch = True
+        sub.dump_outputs = None
         sub.steps, sub.warmup = max(5, min(args.steps, 20)), max(3, min(args.warmup, 5))
         t0 = time.perf_counter()
         try:
@@ -1057,15 +1110,18 @@ def run_inference(args, rank, world, dev):
     ang_t, par_t = ang_t[lo:hi].contiguous().to(dev), {k: v[lo:hi].contiguous().to(dev) for k, v in par_t.items()}
     shifts = ShiftVectors('voxceleb', 15, 6.0, ranges=_direction_ranges())
 
+    e4e_ms = roof = single = e4e_batch = None
     with torch.no_grad():
-        for _ in range(3):                 # warm-up: MIOpen picks its kernels on the first calls
-            source_code = enc(src_img)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(5):
-            source_code = enc(src_img)
-        torch.cuda.synchronize()
-        e4e_ms = (time.perf_counter() - t0) / 5 * 1e3
+        source_code = enc(src_img)
+        if args.full:
+            for _ in range(2):             # warm-up: MIOpen picks its kernels on the first calls
+                source_code = enc(src_img)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                source_code = enc(src_img)
+            torch.cuda.synchronize()
+            e4e_ms = (time.perf_counter() - t0) / 5 * 1e3
         sess = ReenactmentSession(G, A, source_code, 0.7, trunc, batch=B, shifts=shifts, streams=args.streams)
 
         def step1():                       # one batch, start to finish (the roofline pass: kernels of one undisturbed step)
@@ -1086,26 +1142,28 @@ def run_inference(args, rank, world, dev):
             return grid_frames_uint8([src_img, tgt_img[:img.shape[0]], img], swap_rb=True)
 
         elapsed, mine, frames = timed_region(step, args, dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'frames': frames})
         live.flush()
-        e1, _, _ = timed_region(step1, args, dev)
-        single = {'value': round(B * world * args.steps / e1, 2), 'unit': 'frames/s', 'ms_per_step': round(e1 / args.steps * 1e3, 3),
-                  'what': 'every step renders its one batch start to finish (no look-ahead across steps)'}
-        # the same with the session's whole step (DirectionMatrix -> shift -> generator) replayed as ONE hipGraph (graph=True)
-        sess_g = ReenactmentSession(G, A, source_code, 0.7, trunc, batch=B, shifts=shifts, streams=1, graph=True)
+        if args.full:
+            e1, _, _ = timed_region(step1, args, dev)
+            single = {'value': round(B * world * args.steps / e1, 2), 'unit': 'frames/s', 'ms_per_step': round(e1 / args.steps * 1e3, 3),
+                      'what': 'every step renders its one batch start to finish (no look-ahead across steps)'}
+            # the same with the session's whole step (DirectionMatrix -> shift -> generator) replayed as ONE hipGraph (graph=True)
+            sess_g = ReenactmentSession(G, A, source_code, 0.7, trunc, batch=B, shifts=shifts, streams=1, graph=True)
 
-        def step1g():
-            for img in sess_g.frames_for_targets(ang_s, par_s, ang_t, par_t):
-                out = grid_frames_uint8([src_img, tgt_img[:img.shape[0]], img], swap_rb=True)
-            return out
-        eg, _, _ = timed_region(step1g, args, dev)
-        single['session_graph'] = {'value': round(B * world * args.steps / eg, 2), 'ms_per_step': round(eg / args.steps * 1e3, 3),
-                                   'what': 'ReenactmentSession(graph=True): the step as one hipGraph replay'}
-        del sess_g
+            def step1g():
+                for img in sess_g.frames_for_targets(ang_s, par_s, ang_t, par_t):
+                    out = grid_frames_uint8([src_img, tgt_img[:img.shape[0]], img], swap_rb=True)
+                return out
+            eg, _, _ = timed_region(step1g, args, dev)
+            single['session_graph'] = {'value': round(B * world * args.steps / eg, 2), 'ms_per_step': round(eg / args.steps * 1e3, 3),
+                                       'what': 'ReenactmentSession(graph=True): the step as one hipGraph replay'}
+            del sess_g
         assert frames.shape == (hi - lo, args.size, 3 * args.size, 3) and frames.dtype == torch.uint8
         spread = rank_spread((hi - lo) * args.steps, mine, dev, world)
-        roof = roofline_for(args.precision, step1, args.steps, B)
-        e4e_batch = None
-        if not getattr(args, 'skip_e4e_batch', False):     # (the leg of the default run skips it: MIOpen tunes the B=32 shapes for ~20 s)
+        roof = roofline_for(args.precision, step1, args.steps, B) if args.full else unmeasured_roofline(args.precision, NOT_FULL)
+        if args.full and not getattr(args, 'skip_e4e_batch', False):     # (the leg of the default run skips it: MIOpen tunes the B=32 shapes for ~20 s)
             for _ in range(2):
                 enc(tgt_img)
             torch.cuda.synchronize()
@@ -1122,11 +1180,12 @@ def run_inference(args, rank, world, dev):
                     'source|target|reenacted frames; batches stream through ReenactmentSession.streaming() (a step queues its '
                     'batch and finishes the previous one)' % (world, B, args.size, args.cm),
                     {'weight_broadcast_bytes': bcast_bytes, 'weight_broadcast_ms': round(bcast_ms, 2),
-                     'per_rank_frames_per_s_min_max': spread, 'e4e_source_ms': round(e4e_ms, 2),
+                     'per_rank_frames_per_s_min_max': spread, 'e4e_source_ms': round(e4e_ms, 2) if e4e_ms is not None else None,
                      'e4e_batch_images_per_s': round(e4e_batch, 1) if e4e_batch is not None else None,
                      'not_in_the_timed_step': 'DECA / face detection of the targets (out of scope, SURVEY.md §2); e4e of the one source image'})
     out['roofline'] = roof
-    out['one_batch_at_a_time'] = single
+    if single is not None:
+        out['one_batch_at_a_time'] = single
     if args.precision == 'fp16x3':
         out['fp16_saturated_pairs'] = G.saturated_pairs()
     return out
@@ -1193,6 +1252,8 @@ def run_trainer(args, rank, world, dev):
         warnings.simplefilter('ignore')
         elapsed, mine, img = timed_region(step, args, dev)
     assert img.shape == (B, 3, args.size, args.size)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'images': img, 'loss': losses[-1]})
     spread = rank_spread(B * args.steps, mine, dev, world)
     # where the step goes: generator-only legs timed on their own (same shapes), the rest is the loss heads + optimizer
     def gen_only():
@@ -1202,15 +1263,18 @@ def run_trainer(args, rank, world, dev):
         im = generate_image(G, zs, 0.7, trunc, shift_code=A(sv), input_is_latent=False)
         A.zero_grad()
         im.backward(torch.ones_like(im) * 1e-3)
-    for _ in range(2):
-        gen_only()
-    torch.cuda.synchronize()
-    tg = time.perf_counter()
-    for _ in range(args.steps):
-        gen_only()
-    torch.cuda.synchronize()
-    gen_ms = (time.perf_counter() - tg) / args.steps * 1e3
-    roof = roofline_for(args.precision, gen_only, max(2, args.steps // 4), B)
+    gen_ms = None
+    roof = unmeasured_roofline(args.precision, NOT_FULL)
+    if args.full:
+        for _ in range(2):
+            gen_only()
+        torch.cuda.synchronize()
+        tg = time.perf_counter()
+        for _ in range(args.steps):
+            gen_only()
+        torch.cuda.synchronize()
+        gen_ms = (time.perf_counter() - tg) / args.steps * 1e3
+        roof = roofline_for(args.precision, gen_only, max(2, args.steps // 4), B)
     finite = bool(torch.isfinite(torch.stack(losses)).all())
     if rank != 0:
         return None
@@ -1220,8 +1284,9 @@ def run_trainer(args, rank, world, dev):
                     'DECA stand-in (PyTorch-ROCm, random weights), all-reduce of dA, Adam; B=%d per GPU'
                     % (world, args.size, args.cm, B),
                     {'weight_broadcast_bytes': bcast_bytes, 'weight_broadcast_ms': round(bcast_ms, 2),
-                     'per_rank_samples_per_s_min_max': spread, 'generator_only_ms_per_step': round(gen_ms, 3),
-                     'loss_heads_and_optimizer_ms_per_step': round(elapsed / args.steps * 1e3 - gen_ms, 3),
+                     'per_rank_samples_per_s_min_max': spread,
+                     'generator_only_ms_per_step': round(gen_ms, 3) if gen_ms is not None else None,
+                     'loss_heads_and_optimizer_ms_per_step': round(elapsed / args.steps * 1e3 - gen_ms, 3) if gen_ms is not None else None,
                      'losses_finite': finite, 'loss_first_last': [round(float(losses[0]), 5), round(float(losses[-1]), 5)],
                      'fp16_saturated_pairs_fwd_and_bwd': G.saturated_pairs() if args.precision == 'fp16x3' else None,
                      'forward_arithmetic': args.precision,
@@ -1229,8 +1294,9 @@ def run_trainer(args, rank, world, dev):
     out['dtype'] = DTYPE[args.precision] + ('; backward: dL/dx convs in the same fp16 hi+lo arithmetic, range-planned per image from max|g| (bf16 hi+lo with '
                                             'SGDFR_BWD_ARITH=bf16x3), no weight gradients (G frozen), everything else f32' if args.precision != 'fp32' else '')
     out['roofline'] = roof
-    out['roofline']['note'] = ('conv launches of the generator legs of a step (the no-grad forward of 2B rows + grad forward + the dL/dx convs of '
-                               'the backward), loss heads excluded')
+    if args.full:
+        out['roofline']['note'] = ('conv launches of the generator legs of a step (the no-grad forward of 2B rows + grad forward + the dL/dx convs of '
+                                   'the backward), loss heads excluded')
     return out
 
 
@@ -1275,28 +1341,32 @@ def run_pti(args, rank, world, dev):
             opt.step()
             return loss.detach()
         return step
-    eager = make_step(FT.FusedAdam(params, lr=3e-3))
-    e_el, _, l0 = timed_region(eager, args, dev)
-    launches = count_device_launches(eager)
-    with timing.collect() as t:                  # the conv launches of one eager step (forward rows + `bwd ...` rows)
-        eager()
-    torch.cuda.synchronize()
-    conv_s = sum(e0.elapsed_time(e1) for e0, e1, _, _ in t.conv) * 1e-3
-    conv_fl = sum(fl for _, _, fl, _ in t.conv)
+    if args.full:
+        eager = make_step(FT.FusedAdam(params, lr=3e-3))
+        e_el, _, l0 = timed_region(eager, args, dev)
+        launches = count_device_launches(eager)
+        with timing.collect() as t:                  # the conv launches of one eager step (forward rows + `bwd ...` rows)
+            eager()
+        torch.cuda.synchronize()
+        conv_s = sum(e0.elapsed_time(e1) for e0, e1, _, _ in t.conv) * 1e-3
+        conv_fl = sum(fl for _, _, fl, _ in t.conv)
     runner = FT.GraphedStep(make_step(FT.FusedAdam(params, lr=3e-3)), warmup=3, clear_grads_of=list(G.parameters()))
     elapsed, mine, loss = timed_region(runner, args, dev)
-    # the same step computing only the gradients the optimizer reads (finetune.optimize_g(freeze_unused=True)): the weights it
-    # produces are the same, the never-read .grad of the other 5 layers / mapping network is not formed
-    ids = {id(p) for p in params}
-    flags = [(p, p.requires_grad) for p in G.parameters()]
-    for p in G.parameters():
-        p.requires_grad_(id(p) in ids)
-    try:
-        runner2 = FT.GraphedStep(make_step(FT.FusedAdam(params, lr=3e-3)), warmup=3, clear_grads_of=list(G.parameters()))
-        needed_el, _, _ = timed_region(runner2, args, dev)
-    finally:
-        for p, rg in flags:
-            p.requires_grad_(rg)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': loss})
+    if args.full:
+        # the same step computing only the gradients the optimizer reads (finetune.optimize_g(freeze_unused=True)): the weights it
+        # produces are the same, the never-read .grad of the other 5 layers / mapping network is not formed
+        ids = {id(p) for p in params}
+        flags = [(p, p.requires_grad) for p in G.parameters()]
+        for p in G.parameters():
+            p.requires_grad_(id(p) in ids)
+        try:
+            runner2 = FT.GraphedStep(make_step(FT.FusedAdam(params, lr=3e-3)), warmup=3, clear_grads_of=list(G.parameters()))
+            needed_el, _, _ = timed_region(runner2, args, dev)
+        finally:
+            for p, rg in flags:
+                p.requires_grad_(rg)
     if rank != 0:
         return None
     # algorithmic work of a step: forward convs + dL/dx convs + dL/dW convs = 3 x the forward's conv FLOPs; bytes:
@@ -1315,16 +1385,17 @@ def run_pti(args, rank, world, dev):
                     'convs[4..11] of Generator(%d,cm=%d), the step replayed as ONE hipGraph (finetune.GraphedStep)' % (world, args.size, args.cm),
                     {'optimised_parameters': w_opt, 'generator_parameters': w_all})
     out['config']['per_gpu_batch'] = out['config']['global_batch'] = B
-    out['eager'] = {'ms_per_step': round(e_el / args.steps * 1e3, 3), 'device_launches_per_step': launches,
-                    'conv_launches_per_step': len(t.conv), 'conv_ms_per_step': round(conv_s * 1e3, 3),
-                    'conv_tflops': round(conv_fl / conv_s / 1e12, 2) if conv_s else None}
-    out['needed_gradients_only'] = {'ms_per_step': round(needed_el / args.steps * 1e3, 3),
-                                    'what': 'optimize_g(freeze_unused=True): only the gradients Adam reads (convs[4..11]); same updated weights'}
-    out['launches_per_step'] = launches
+    if args.full:
+        out['eager'] = {'ms_per_step': round(e_el / args.steps * 1e3, 3), 'device_launches_per_step': launches,
+                        'conv_launches_per_step': len(t.conv), 'conv_ms_per_step': round(conv_s * 1e3, 3),
+                        'conv_tflops': round(conv_fl / conv_s / 1e12, 2) if conv_s else None}
+        out['needed_gradients_only'] = {'ms_per_step': round(needed_el / args.steps * 1e3, 3),
+                                        'what': 'optimize_g(freeze_unused=True): only the gradients Adam reads (convs[4..11]); same updated weights'}
+        out['launches_per_step'] = launches
+        out['loss_first_last'] = [round(float(l0), 6), round(float(loss), 6)]
     out['tflops'] = round(step_gflop / ms, 2)          # GFLOP / ms = TFLOP/s
     out['hbm_gbs'] = round(step_bytes / (ms * 1e-3) / 1e9, 1)
     out['hbm_frac'] = round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-    out['loss_first_last'] = [round(float(l0), 6), round(float(loss), 6)]
     peak = FP32_MFMA_PEAK_TFLOPS
     out['roofline'] = {'bound': 'mfma', 'kernel': 'whole PTI step (forward + dL/dx + dL/dW convs; fp32-grade arithmetic)', 'achieved': out['tflops'],
                        'peak': peak, 'unit': 'TFLOP/s', 'frac': round(out['tflops'] / peak, 4), 'traffic': None,

@@ -1,6 +1,6 @@
 # same-box A/B of environment switches on the headline bench:  bash scripts/env_ab.sh "SGDFR_X=0" "SGDFR_X=1" ...
 # (prints value / unverified / single-stream frames/s, conv ms, and the per-launch rows matching $AB_GREP)
-B="python bench.py --no-cpu-baseline --no-alt --no-other-configs --no-oracle-delta --sustain 0 --layers --steps 30 --warmup 10"
+B="python bench.py --full --no-cpu-baseline --no-alt --no-other-configs --no-oracle-delta --sustain 0 --layers --steps 30 --warmup 10"
 for cfg in "$@"; do
   echo "=== $cfg"
   env $cfg $B 2> gpurun_out/ab_layers.txt | python -c "

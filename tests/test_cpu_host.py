@@ -313,3 +313,23 @@ def test_bench_kernel_families_name_the_kernel_that_runs_a_row():
     assert bench._family('bwd split3 256->256 @64x64', 16) == 'bwd split3'
     assert bench.row_peak('wsplit F(4,3) 512->512 @32x32 [f8 cross]', bench.SPLIT_PEAK_TFLOPS) == bench.F8_CROSS_PEAK_TFLOPS
     assert abs(bench.F8_CROSS_PEAK_TFLOPS - 1666.7) < 0.1
+
+
+def test_bench_dump_outputs_float32_and_a_fixed_sample_past_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): float32 .npy files, integer outputs converted exactly; arrays that together pass
+    DUMP_BYTES are cut to their share of it, at the same seeded positions in every run."""
+    import numpy as np
+    import bench
+    img = torch.arange(24, dtype=torch.float32).reshape(2, 3, 4)
+    frames = torch.arange(200, dtype=torch.uint8).reshape(2, 100)
+    bench.dump_outputs(str(tmp_path / 'a'), {'images': img, 'frames': frames})
+    a = np.load(str(tmp_path / 'a' / 'images.npy'))
+    f = np.load(str(tmp_path / 'a' / 'frames.npy'))
+    assert a.dtype == f.dtype == np.float32 and np.array_equal(a, img.numpy()) and np.array_equal(f, frames.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4 * 112)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), {'images': img, 'frames': frames})
+    sa, sf = np.load(str(tmp_path / 'b' / 'images.npy')), np.load(str(tmp_path / 'b' / 'frames.npy'))
+    assert sa.nbytes + sf.nbytes <= 4 * 112 and sa.size == 24 * 112 // 224 and sf.size == 200 * 112 // 224
+    assert set(sf.tolist()) <= set(range(200)) and len(set(sf.tolist())) == sf.size          # distinct elements of the output
+    assert np.array_equal(sa, np.load(str(tmp_path / 'c' / 'images.npy'))) and np.array_equal(sf, np.load(str(tmp_path / 'c' / 'frames.npy')))

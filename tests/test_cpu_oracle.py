@@ -66,7 +66,10 @@ def test_kat4_generator256_cm1():
         assert maxabs(trunc, t(g['cm1.trunc'])) <= 1e-6
         img, lat = O.generator_forward(P, [S.synthetic_z(SEED, 2, key='kat4.z')], return_latents=True,
                                        truncation=0.7, truncation_latent=trunc)
-        assert maxabs(lat, t(g['cm1.lat_z'])) <= 1e-6
+        # the reference captured on MKL's AVX-512 path and on its generic path (AMD hosts; oracle/make_golden_generic_blas.py): the
+        # fp32 mapping network sums in the order of whichever path this host's MKL takes
+        gb = golden('kat4_generic_blas.npz')
+        assert min(maxabs(lat, t(g['cm1.lat_z'])), maxabs(lat, t(gb['cm1.lat_z']))) <= 1e-6
         _digest_ok(img, g, 'cm1.z')
         w = S.synthetic_latents(SEED, 2, key='kat4.w')
         img, _ = O.generator_forward(P, [w], input_is_latent=True)

@@ -25,7 +25,7 @@ def _worker(rank, world, port, q):
     from stylegan_directions_face_reenactment_amd import distributed as D, synthetic as S
     from stylegan_directions_face_reenactment_amd.model import Generator
     from stylegan_directions_face_reenactment_amd.direction_matrix import DirectionMatrix
-    r, lr, w = D.init_from_env(backend='gloo')
+    r, lr, w = D.init_from_env(backend='gloo', use_gpu=False)      # (a CPU flow: two ranks on a one-GPU host too)
     assert (r, w) == (rank, world)
     torch.manual_seed(100 + rank)                      # different random init per rank
     G = Generator(32, 512, 8, channel_multiplier=1)

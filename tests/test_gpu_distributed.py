@@ -60,7 +60,7 @@ def test_rccl_one_rank_group_on_this_gpu():
 
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_sharing_this_gpu_over_gloo():
-    r, line = _run_bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '4', '--size', '64', '--no-alt',
+    r, line = _run_bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '4', '--size', '64', '--full', '--no-alt',
                          '--no-cpu-baseline', env={'SGDFR_ALLOW_GPU_SHARING': '1', 'SGDFR_DIST_BACKEND': 'gloo'}, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]
     assert line['n_gpus'] == 2 and line['config']['global_batch'] == 8 and line['value'] > 0
@@ -162,11 +162,11 @@ def test_bench_refuses_two_ranks_on_one_gpu():
 
 @pytest.mark.timeout(1500)
 def test_bench_inference_and_trainer_configs_small():
-    r, line = _run_bench('--config', 'inference', '--steps', '2', '--warmup', '1', '--batch', '4', timeout=700)
+    r, line = _run_bench('--config', 'inference', '--full', '--steps', '2', '--warmup', '1', '--batch', '4', timeout=700)
     assert r.returncode == 0, r.stderr[-3000:]
     assert line['n_gpus'] == 1 and line['unit'] == 'frames/s' and line['value'] > 0
     assert line['_detail']['roofline']['per_layer'] and line['config']['e4e_source_ms'] > 0
-    r, line = _run_bench('--config', 'trainer', '--steps', '2', '--warmup', '1', '--batch', '4', timeout=700)
+    r, line = _run_bench('--config', 'trainer', '--full', '--steps', '2', '--warmup', '1', '--batch', '4', timeout=700)
     assert r.returncode == 0, r.stderr[-3000:]
     assert line['unit'] == 'samples/s' and line['value'] > 0
     compact, line = line, line['_detail']          # (the long-form record; the compact line keeps value / roofline / the leg scalars)
@@ -178,3 +178,28 @@ def test_bench_inference_and_trainer_configs_small():
     assert line['roofline']['frac'] > 0 and line['config']['generator_only_ms_per_step'] > 0
     first, last = line['config']['loss_first_last']
     assert first > 0 and last > 0
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times K steps of the headline path only, and --dump-outputs writes the images its last timed step
+    returned: float32, the timed batch's shape, within the oracle bar on the bench's own seeded latents and weights."""
+    import numpy as np
+    from util import O
+    import bench
+    from stylegan_directions_face_reenactment_amd import synthetic as S
+    r, line = _run_bench('--steps', '3', '--warmup', '1', '--batch', '4', '--size', '64', '--dump-outputs', str(tmp_path), timeout=540)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+    assert abs(line['value'] - 4 * 1e3 / line['ms_per_step']) <= 1e-3 * line['value']
+    # nothing beside the headline was measured
+    assert 'legs' not in line and 'max_abs_vs_oracle' not in line and line['roofline']['achieved'] is None
+    assert line['cpu_baseline']['value'] is None
+    img = np.load(str(tmp_path / 'images.npy'))
+    assert img.dtype == np.float32 and img.shape == (4, 3, 64, 64) and np.isfinite(img).all()
+    G, template = bench.generator_state_template(64, 1)
+    state = S.synthetic_state_dict(template, seed=bench.SEED)
+    w = S.synthetic_latents(bench.SEED, 4, n_latent=G.n_latent, key='bench.w')
+    with torch.no_grad():
+        ref, _ = O.generator_forward(state, [w], input_is_latent=True)
+    assert float(np.abs(img.astype(np.float64) - ref.double().numpy()).max()) <= 1e-3
