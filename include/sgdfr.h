@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SGDFR_ABI_VERSION 22
+#define SGDFR_ABI_VERSION 23
 
 /* modes of sgdfr_modconv2d_fwd_f32 */
 #define SGDFR_MODE_PLAIN3 0 /* 3x3, pad 1, same resolution                      (model.py:267-271) */
@@ -565,6 +565,29 @@ int sgdfr_modconv_wgrad_finish_parts_f32(const float* part, int ksplit, const fl
 int sgdfr_modconv_wgrad_finish_parts_oik_f32(const float* part, int ksplit, const float* weight, const float* dq, const float* a,
                                              int64_t a_stride, const float* d, const float* s, int B, float* dweight, int Cout, int Cin,
                                              void* stream);
+
+/* LPIPS (AlexNet, v0.1) distance and its input gradient (libs/criteria/lpips/lpips.py:28-34, networks.py:53-63,78-85, utils.py:6-12),
+ * csrc/lpips.hip.  Images x, y [rows,3,H,W] fp32 in [-1,1], H, W in 31..4096 (unsupported sizes return an error).
+ * sgdfr_lpips_prepack_f32: params = host array of 17 device pointers in the order conv0 weight, conv0 bias, conv3 w, b, conv6 w, b,
+ *   conv8 w, b, conv10 w, b (torchvision layout [Cout][Cin][k][k]), mean[3], std[3], lin0..lin4 ([C_t] each) -> pack of
+ *   sgdfr_lpips_pack_elems() floats (forward and flipped input-gradient weights; rebuild it whenever a parameter changes).
+ * sgdfr_lpips_features_f32: the five post-ReLU taps of rows_x images of x followed by rows_y images of y (y may be NULL with
+ *   rows_y = 0) into feats (sgdfr_lpips_feature_elems(rows_x + rows_y) floats: tap t is [rows, C_t, h_t, w_t], taps in order).
+ * sgdfr_lpips_distance_f32: loss[0] = (1/B) sum_t sum_b mean_hw sum_c lin_t[c] (n_x - n_y)^2 between images 0..B-1 of fx (rows_x
+ *   rows) and images y_row0.. of fy (rows_y rows; y_bcast 1: image y_row0 for every b).
+ * sgdfr_lpips_backward_f32: dx [B,3,H,W] = grad_loss[0] (device scalar) * dL/dx of that distance; the gradient of y is not formed.
+ * workspace: device scratch of at least sgdfr_lpips_workspace_bytes(B, H, W) bytes (its size passed as workspace_bytes), B = the
+ *   batch of x; features accept rows_x + rows_y in {B, 2B}.  Deterministic (no float atomics), no host synchronisation. */
+int64_t sgdfr_lpips_pack_elems(void);
+int64_t sgdfr_lpips_feature_elems(int rows, int H, int W);
+int64_t sgdfr_lpips_workspace_bytes(int B, int H, int W);
+int sgdfr_lpips_prepack_f32(const float* const* params, float* pack, void* stream);
+int sgdfr_lpips_features_f32(const float* x, int rows_x, const float* y, int rows_y, int H, int W, const float* pack, float* feats,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_lpips_distance_f32(const float* fx, int rows_x, const float* fy, int rows_y, int y_row0, int y_bcast, int B, int H, int W,
+                             const float* pack, float* loss, void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_lpips_backward_f32(const float* grad_loss, const float* fx, int rows_x, const float* fy, int rows_y, int y_row0, int y_bcast,
+                             int B, int H, int W, const float* pack, float* dx, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio

@@ -23,7 +23,7 @@ if os.environ.get('SGDFR_LIB'):
     else:
         import warnings as _warnings
         _warnings.warn('SGDFR_LIB is set but ignored (set SGDFR_ALLOW_LIB_OVERRIDE=1 to load a probe build)', RuntimeWarning)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _c_f32p = ctypes.c_void_p
 _i, _i64, _f = ctypes.c_int, ctypes.c_int64, ctypes.c_float
@@ -157,6 +157,13 @@ SIGNATURES['sgdfr_modconv2d_wsplit_f32'] = [ctypes.c_void_p, ctypes.c_void_p, _c
 SIGNATURES['sgdfr_fused_bias_act'] = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i64, _i, _i, _i, _i, _f, _f, _i,
                                       ctypes.c_void_p]
 SIGNATURES['sgdfr_upfirdn2d'] = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p] + [_i] * 15 + [ctypes.c_void_p]
+SIGNATURES['sgdfr_lpips_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_lpips_features_f32'] = [_c_f32p, _i, _c_f32p, _i, _i, _i, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+SIGNATURES['sgdfr_lpips_distance_f32'] = [_c_f32p, _i, _c_f32p, _i, _i, _i, _i, _i, _i, _c_f32p, _c_f32p, ctypes.c_void_p, _i64,
+                                          ctypes.c_void_p]
+SIGNATURES['sgdfr_lpips_backward_f32'] = [_c_f32p, _c_f32p, _i, _c_f32p, _i, _i, _i, _i, _i, _i, _c_f32p, _c_f32p, ctypes.c_void_p, _i64,
+                                          ctypes.c_void_p]
+LPIPS_PARAMS = 17       # pointers sgdfr_lpips_prepack_f32 takes
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
 OPTIONAL_SIGNATURES = {'sgdfr_mfma_ceiling_probe': [_i, _i, _i, _i, _i, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]}
@@ -186,6 +193,11 @@ def load():
     lib.sgdfr_modconv_prepack_split_elems.restype = ctypes.c_int64
     lib.sgdfr_modconv_prepack_wsplit_elems.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.sgdfr_modconv_prepack_wsplit_elems.restype = ctypes.c_int64
+    lib.sgdfr_lpips_pack_elems.argtypes = []
+    lib.sgdfr_lpips_pack_elems.restype = ctypes.c_int64
+    for name in ('sgdfr_lpips_feature_elems', 'sgdfr_lpips_workspace_bytes'):
+        getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        getattr(lib, name).restype = ctypes.c_int64
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():

@@ -1,6 +1,6 @@
 """Generator fine-tuning on one source (PTI), the counterpart of libs/optimization.py:25-72 (`optimize_g`): same parameter
-selection, optimiser and truncation; the perceptual loss is the caller's (LPIPS and the losses around it are neighbours of
-the hot path).  The step -- forward, backward through autograd.SynthesisFn, Adam -- can be captured once and
+selection, optimiser and truncation.  The default loss is the L2 term alone (l2_loss_fn); PtiLoss is the reference's
+100 * MSE + LPIPS(alex) on the HIP LPIPS (lpips.py), its target features cached once per source.  The step -- forward, backward through autograd.SynthesisFn, Adam -- can be captured once and
 replayed as a hipGraph: at one source per step the eager step is bound by its host launches (~5 ms), the replay takes
 3.4-3.8 ms (bench.py --config pti, scripts/pti_step_bench.py)."""
 import torch
@@ -19,6 +19,32 @@ def pti_parameters(generator, optimize_all=False):
 def l2_loss_fn(imgs_gen, real_imgs, pt_l2_lambda):
     """The L2 term of calc_loss (libs/criteria/l2_loss.py: mse) weighted as optimization.py does; stand-in default."""
     return pt_l2_lambda * torch.nn.functional.mse_loss(imgs_gen, real_imgs)
+
+
+class PtiLoss:
+    """The PTI loss of libs/criteria/PTI/base_coach.py:24-43 (calc_loss, use_ball_holder off): pt_l2_lambda * mse +
+    pt_lpips_lambda * LPIPS(alex) (hyperparameters.py: pt_lpips_lambda = 1), callable as optimize_g's loss_fn.  The features of
+    the fixed real image are computed once, here (before any capture); an eager call checks that it is handed the same image,
+    unchanged (a captured replay cannot look, so do not write into real_imgs between replays)."""
+
+    def __init__(self, lpips, real_imgs, pt_lpips_lambda=1.0):
+        self.lpips = lpips
+        self.pt_lpips_lambda = float(pt_lpips_lambda)
+        self.real = real_imgs.detach()
+        self.target = lpips.target(self.real)
+
+    def _check(self, real_imgs):
+        r = self.real
+        if real_imgs.data_ptr() != r.data_ptr() or real_imgs.shape != r.shape or real_imgs.stride() != r.stride():
+            raise RuntimeError('PtiLoss: called with a different real image than it was built for')
+        if real_imgs._version != self.target.source_version:
+            raise RuntimeError('PtiLoss: the real image was modified in place after its LPIPS features were cached')
+
+    def __call__(self, imgs_gen, real_imgs, pt_l2_lambda):
+        if not torch.cuda.is_current_stream_capturing():
+            self._check(real_imgs)
+        loss = torch.nn.functional.mse_loss(imgs_gen, real_imgs) * pt_l2_lambda
+        return loss + self.lpips(imgs_gen, self.target) * self.pt_lpips_lambda
 
 
 class FusedAdam:

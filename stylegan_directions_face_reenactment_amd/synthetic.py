@@ -183,3 +183,21 @@ def synthetic_encoder_state(template, seed=0):
         else:
             raise KeyError(key)
     return out
+
+
+def synthetic_lpips_state(seed):
+    """Seeded LPIPS-alex state dict in the reference's keys (lpips.LPIPS): conv weights at He scale, small biases, `lin` weights
+    |N(0, 0.1)| -- non-negative like the trained heads; mean / std are the constants of networks.py:55-58."""
+    from collections import OrderedDict
+    chans = (3, 64, 192, 384, 256, 256)
+    ks = (11, 5, 3, 3, 3)
+    sd = OrderedDict()
+    sd['net.mean'] = torch.tensor([-.030, -.088, -.188]).view(1, 3, 1, 1)
+    sd['net.std'] = torch.tensor([.458, .448, .450]).view(1, 3, 1, 1)
+    for t, i in enumerate((0, 3, 6, 8, 10)):
+        cin, cout, k = chans[t], chans[t + 1], ks[t]
+        sd['net.layers.%d.weight' % i] = counter_tensor(seed, 'lpips.w%d' % i, (cout, cin, k, k), 0.0, (2.0 / (cin * k * k)) ** 0.5)
+        sd['net.layers.%d.bias' % i] = counter_tensor(seed, 'lpips.b%d' % i, (cout,), 0.0, 0.01)
+    for t in range(5):
+        sd['lin.%d.1.weight' % t] = counter_tensor(seed, 'lpips.lin%d' % t, (1, chans[t + 1], 1, 1), 0.0, 0.1).abs()
+    return sd
