@@ -589,6 +589,31 @@ int sgdfr_lpips_distance_f32(const float* fx, int rows_x, const float* fy, int r
 int sgdfr_lpips_backward_f32(const float* grad_loss, const float* fx, int rows_x, const float* fy, int rows_y, int y_row0, int y_bcast,
                              int B, int H, int W, const float* pack, float* dx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ArcFace identity-loss backbone, IR-SE-50 at 112x112 in eval mode (libs/criteria/id_loss.py:20-25, model_irse.py:9-48,
+ * helpers.py:57-121), csrc/idloss.hip.  Images x, y [rows,3,H,W] fp32; crop 1 takes [35:223, 32:220] with PyTorch slice clamping,
+ * crop 0 the whole image; then AdaptiveAvgPool2d(112).  An empty window or a side above 8192 returns an error.
+ * sgdfr_idloss_prepack_f32: params = host array of 245 device pointers with every BatchNorm folded on the host:
+ *   stem w0 [64,3,3,3] (BN folded), b0 [64], PReLU a0 [64];
+ *   per unit (24): BN1 scale s1 [Cin], shift t1 [Cin], conv1 w1 [D,Cin,3,3], PReLU a1 [D], conv2 w2 [D,D,3,3] (BN2 folded), b2 [D],
+ *     SE fc1 [D/16,D], fc2 [D,D/16], shortcut conv wsc [D,Cin] (BN folded), bsc [D] (both NULL where Cin == D);
+ *   head wh [512,25088] (BN2d and BN1d folded), bh [512]
+ *   -> pack of sgdfr_idloss_pack_elems() floats (forward and input-gradient weights; rebuild it whenever a parameter changes).
+ * sgdfr_idloss_forward_f32: emb [rows_x + rows_y, 512] = l2-normalised embeddings of the rows of x followed by those of y (y may
+ *   be NULL with rows_y = 0; rows_y <= rows_x).  The split-K plan follows rows_x, so x's results do not depend on rows_y.
+ *   saved (NULL: nothing is kept) receives sgdfr_idloss_saved_elems(rows_x) floats for the backward.
+ * sgdfr_idloss_backward_f32: dx [rows,3,H,W] = dL/dx for grad_emb [rows,512] = dL/de of x's embeddings, from the saved buffer of a
+ *   forward with rows_x = rows, the same H, W, crop and pack.  Zero outside the crop window.
+ * workspace: device scratch of at least sgdfr_idloss_workspace_bytes(rows, H, W) bytes, rows = rows_x + rows_y for the forward.
+ * Deterministic (no float atomics), no host synchronisation, everything on `stream`. */
+int64_t sgdfr_idloss_pack_elems(void);
+int64_t sgdfr_idloss_saved_elems(int rows);
+int64_t sgdfr_idloss_workspace_bytes(int rows, int H, int W);
+int sgdfr_idloss_prepack_f32(const float* const* params, float* pack, void* stream);
+int sgdfr_idloss_forward_f32(const float* x, int rows_x, const float* y, int rows_y, int H, int W, int crop, const float* pack,
+                             float* emb, float* saved, void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_idloss_backward_f32(const float* grad_emb, const float* saved, int rows, int H, int W, int crop, const float* pack,
+                              float* dx, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

@@ -7,10 +7,12 @@
 Only the modules of the hot path are aliased; everything else under ``libs`` keeps
 resolving to the reference checkout on sys.path.  ``install_lpips(state_dict)`` (opt-in) additionally mounts the HIP LPIPS at
 ``libs.criteria.lpips.lpips`` so that unchanged ``LPIPS(net_type='alex')`` calls get it with those weights (no torchvision, no
-download).  ``libs.utilities.generic`` is NOT replaced wholesale
+download); ``install_id_loss(path)`` (opt-in) mounts the HIP identity loss at ``libs.criteria.id_loss`` the same way.
+``libs.utilities.generic`` is NOT replaced wholesale
 (it also holds DECA glue); call ``patch_generic(module)`` to swap in the two fused functions.
 """
 import importlib
+import os
 import sys
 import types
 
@@ -46,16 +48,7 @@ def install_lpips(state_dict):
     from . import lpips as hip_lpips
     sd = dict(state_dict)
     hip_lpips.LPIPS().load_state_dict(sd)           # fail here, not at the first LPIPS() of the caller
-    parts = LPIPS_ALIAS.split('.')
-    for i in range(1, len(parts)):
-        name = '.'.join(parts[:i])
-        if name not in sys.modules:
-            try:
-                importlib.import_module(name)
-            except ImportError:
-                pkg = types.ModuleType(name)
-                pkg.__path__ = []
-                sys.modules[name] = pkg
+    _parent_packages(LPIPS_ALIAS)
 
     class LPIPS(hip_lpips.LPIPS):
         def __init__(self, net_type: str = 'alex', version: str = '0.1'):
@@ -66,6 +59,54 @@ def install_lpips(state_dict):
     mod = types.ModuleType(LPIPS_ALIAS)
     mod.LPIPS = LPIPS
     mod.__doc__ = 'HIP LPIPS mounted by stylegan_directions_face_reenactment_amd.compat.install_lpips'
-    sys.modules[LPIPS_ALIAS] = mod
-    setattr(sys.modules['.'.join(parts[:-1])], parts[-1], mod)
+    _mount(LPIPS_ALIAS, mod)
     return LPIPS_ALIAS
+
+
+def _parent_packages(alias):
+    """Import the parent packages of `alias`; those that cannot be imported are created empty."""
+    parts = alias.split('.')
+    for i in range(1, len(parts)):
+        name = '.'.join(parts[:i])
+        if name not in sys.modules:
+            try:
+                importlib.import_module(name)
+            except ImportError:
+                pkg = types.ModuleType(name)
+                pkg.__path__ = []
+                sys.modules[name] = pkg
+
+
+def _mount(alias, mod):
+    parent, _, leaf = alias.rpartition('.')
+    sys.modules[alias] = mod
+    setattr(sys.modules[parent], leaf, mod)
+
+
+ID_LOSS_ALIAS = 'libs.criteria.id_loss'
+ID_LOSS_DEFAULT_PATH = './pretrained_models/model_ir_se50.pth'     # id_loss.py:8
+
+
+def install_id_loss(pretrained_model_path=None):
+    """Mount a module at libs.criteria.id_loss whose IDLoss(pretrained_model_path) is the HIP IDLoss: an unchanged
+    `id_loss.IDLoss().cuda().eval()` (utils_train.py:53) loads `pretrained_model_path` (default: the reference's
+    ./pretrained_models/model_ir_se50.pth) itself, and a missing file prints and exits as id_loss.py:12-14 does.  Parent
+    packages that cannot be imported are created empty."""
+    from . import id_loss as hip_id_loss
+    default = pretrained_model_path or ID_LOSS_DEFAULT_PATH
+    _parent_packages(ID_LOSS_ALIAS)
+
+    class IDLoss(hip_id_loss.IDLoss):
+        def __init__(self, pretrained_model_path=default):
+            print('Loading ResNet ArcFace for identity loss')
+            if not os.path.exists(pretrained_model_path):
+                print('ir_se50 model does not exist in {}'.format(pretrained_model_path))
+                sys.exit()
+            super().__init__(pretrained_model_path)
+
+    mod = types.ModuleType(ID_LOSS_ALIAS)
+    mod.IDLoss = IDLoss
+    mod.Backbone = hip_id_loss.Backbone
+    mod.__doc__ = 'HIP identity loss mounted by stylegan_directions_face_reenactment_amd.compat.install_id_loss'
+    _mount(ID_LOSS_ALIAS, mod)
+    return ID_LOSS_ALIAS

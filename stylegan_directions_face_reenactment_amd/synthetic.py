@@ -201,3 +201,35 @@ def synthetic_lpips_state(seed):
     for t in range(5):
         sd['lin.%d.1.weight' % t] = counter_tensor(seed, 'lpips.lin%d' % t, (1, chans[t + 1], 1, 1), 0.0, 0.1).abs()
     return sd
+
+
+def synthetic_arcface_state(seed):
+    """Seeded IR-SE-50 state dict in model_irse.Backbone(112, 50, 'ir_se')'s keys (id_loss.Backbone), scaled like
+    synthetic_encoder_state: conv filters N(0, 0.7/fan_in), BatchNorm statistics near (0, 1), PReLU slopes near 0.25, SE
+    filters N(0, 1/fan_in); the Linear 25088->512 N(0, 1/25088) with a small bias."""
+    from collections import OrderedDict
+    from .id_loss import Backbone
+    out = OrderedDict()
+    for key, t in Backbone().state_dict().items():
+        shape = tuple(t.shape)
+        if key.endswith('num_batches_tracked'):
+            out[key] = torch.zeros(shape, dtype=torch.int64)
+        elif key.endswith('running_var'):
+            v = counter_normal(seed, key, int(np.prod(shape))) * 0.2 + 1.0
+            out[key] = torch.from_numpy(np.maximum(v, 0.3).astype(np.float32).reshape(shape))
+        elif key.endswith('running_mean'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.1)
+        elif len(shape) == 4:                                     # conv filters; SE fc1 / fc2 are 1x1 convs
+            fan_in = shape[1] * shape[2] * shape[3]
+            gain = 1.0 if '.res_layer.5.' in key else 0.7
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(gain / fan_in)))
+        elif len(shape) == 2:                                     # output_layer.3: Linear 25088 -> 512
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(1.0 / shape[1])))
+        elif key.endswith('.bias'):                               # BatchNorm shift, Linear bias
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.05)
+        elif key.endswith('.weight'):                             # 1-D: BatchNorm scale or PReLU slope
+            is_prelu = key == 'input_layer.2.weight' or key.endswith('res_layer.2.weight')
+            out[key] = counter_tensor(seed, key, shape, 0.25 if is_prelu else 1.0, 0.05 if is_prelu else 0.1)
+        else:
+            raise KeyError(key)
+    return out
