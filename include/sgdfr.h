@@ -614,6 +614,44 @@ int sgdfr_idloss_forward_f32(const float* x, int rows_x, const float* y, int row
 int sgdfr_idloss_backward_f32(const float* grad_emb, const float* saved, int rows, int H, int W, int crop, const float* pack,
                               float* dx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* FLAME decode at DECA's sizes, its backward to the 3DMM coefficients, and the shape / mouth / eye L1 terms
+ * (libs/DECA/decalib/deca.py:229-239, models/FLAME.py:175-214, models/lbs.py, utils/util.py:227-237, libs/criteria/losses.py:20-62),
+ * csrc/flame.hip.  Sizes are fixed: 5023 vertices, 150 shape + expression components, 36 pose-corrective components, 5 joints with
+ * parents [-1,0,1,1,1] and zero neck / eye poses, 68 + 68 landmarks, 79 dynamic contour rows.
+ * sgdfr_flame_prepack_f32: params = host array of 15 device pointers: v_template [5023*3], shapedirs [5023*3][150], posedirs
+ *   [36][5023*3], lbs_weights [5023][5], the joint regressor folded on the host, J_template [5*3] and Jdirs [5*3][150]
+ *   (J = J_template + Jdirs . betas), the corner vertices (int32) and barycentric weights of the static [51][3], full [68][3] and
+ *   dynamic [79][17][3] landmarks, and the inverse landmark index: offsets [5024] (int32), slots [n_csr] (int32: 0..50 static,
+ *   51..118 full, 119 + 17 * row + j dynamic) and weights [n_csr] -> pack of sgdfr_flame_pack_elems() floats.  The size arguments
+ *   are checked against the sizes above (n_csr = 4386).
+ * sgdfr_flame_decode_f32: rows coefficient sets (shape [rows,100], exp [rows,50], pose [rows,6]) followed by rows_b sets of a second
+ *   group (may be NULL with rows_b = 0), R = rows + rows_b.  project 1: cam [R,3] -> landmarks2d [R,68,2], landmarks3d [R,68,3],
+ *   trans_verts [R,5023,3] in pixels of a 224-pixel image; project 0: the FLAME.forward triple, landmarks2d [R,68,3], landmarks3d
+ *   [R,68,3], trans_verts and cam unused.  saved receives sgdfr_flame_saved_elems(R) floats: per row 256 floats of pose state (the
+ *   dynamic contour row as int32 at index 201), v_posed [5023*3] and the un-projected vertices [5023*3]; a row range of it serves the
+ *   backward of that range.
+ * sgdfr_flame_decode_backward_f32: dshape [rows,100], dexp [rows,50], dpose [rows,6], dcam [rows,3] (may be NULL) for cotangents of
+ *   the three outputs (each may be NULL = zero), times gscale[0] when gscale (device scalar) is given; the dynamic row is a constant.
+ * sgdfr_shape_loss_f32: landmarks2d [2*rows,68,2] and trans_verts [2*rows,5023,3] hold the ground-truth rows followed by the
+ *   reenacted rows.  loss[0] = total; terms[0..2] = lambda-weighted shape / mouth / eye terms, terms[3..5] the plain terms (8 floats);
+ *   g_landmarks2d [rows,68,2] and g_trans_verts [rows,5023,3] receive the cotangents of the total for the reenacted rows.
+ * workspace: device scratch of at least sgdfr_flame_workspace_bytes(rows) bytes.  Deterministic (no float atomics), no host
+ * synchronisation, everything on `stream`: 3 launches per decode, 2 per loss, 2 per backward. */
+int64_t sgdfr_flame_pack_elems(void);
+int64_t sgdfr_flame_saved_elems(int rows);
+int64_t sgdfr_flame_workspace_bytes(int rows);
+int sgdfr_flame_prepack_f32(const void* const* params, int n_vertices, int n_betas, int n_pose_feature, int n_joints, int n_dynamic_rows,
+                            int n_csr, float* pack, void* stream);
+int sgdfr_flame_decode_f32(const float* shape, const float* exp, const float* pose, int rows, const float* shape_b, const float* exp_b,
+                           const float* pose_b, int rows_b, const float* cam, const float* pack, int project, float* landmarks2d,
+                           float* landmarks3d, float* trans_verts, float* saved, void* stream);
+int sgdfr_flame_decode_backward_f32(const float* g_landmarks2d, const float* g_landmarks3d, const float* g_trans_verts,
+                                    const float* gscale, int rows, const float* pack, int project, const float* saved, float* dshape,
+                                    float* dexp, float* dpose, float* dcam, void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_shape_loss_f32(const float* landmarks2d, const float* trans_verts, int rows, float lambda_shape, float lambda_mouth,
+                         float lambda_eye, float* loss, float* terms, float* g_landmarks2d, float* g_trans_verts, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

@@ -233,3 +233,81 @@ def synthetic_arcface_state(seed):
         else:
             raise KeyError(key)
     return out
+
+
+def _counter_index(seed, key, shape, n):
+    """Integers in 0..n-1 from the counter generator."""
+    count = int(np.prod(shape))
+    v = (np.abs(counter_normal(seed, key, count)) * 1e7).astype(np.int64) % n
+    return torch.from_numpy(v.reshape(tuple(shape)))
+
+
+def _counter_simplex(seed, key, shape, floor=0.0):
+    """Non-negative rows that sum to 1 along the last axis."""
+    v = np.abs(counter_normal(seed, key, int(np.prod(shape)))).reshape(tuple(shape)) + floor
+    return torch.from_numpy((v / v.sum(-1, keepdims=True)).astype(np.float32))
+
+
+def synthetic_flame_state(seed):
+    """Seeded FLAME state dict of DECA's sizes in the keys of models/FLAME.py (flame.FLAME): template N(0, 0.08), blend-shape and
+    pose-corrective bases N(0, 0.002), non-negative joint-regressor and skinning rows that sum to 1, valid face indices and
+    barycentric triples that sum to 1.  24 MB: regenerated from the seed wherever it is needed, never stored."""
+    from collections import OrderedDict
+    from . import flame as FL
+    V, Fc = FL.V, FL.FACES
+    sd = OrderedDict()
+    sd['faces_tensor'] = _counter_index(seed, 'flame.f', (Fc, 3), V)
+    sd['v_template'] = counter_tensor(seed, 'flame.v_template', (V, 3), 0.0, 0.08)
+    sd['shapedirs'] = counter_tensor(seed, 'flame.shapedirs', (V, 3, FL.N_SHAPE + FL.N_EXP), 0.0, 0.002)
+    sd['posedirs'] = counter_tensor(seed, 'flame.posedirs', (FL.N_POSE_FEATURE, 3 * V), 0.0, 0.002)
+    sd['J_regressor'] = _counter_simplex(seed, 'flame.J_regressor', (FL.JOINTS, V))
+    sd['parents'] = torch.tensor(FL.PARENTS, dtype=torch.long)
+    sd['lbs_weights'] = _counter_simplex(seed, 'flame.weights', (V, FL.JOINTS))
+    sd['eye_pose'] = torch.zeros(1, 6)
+    sd['neck_pose'] = torch.zeros(1, 3)
+    sd['lmk_faces_idx'] = _counter_index(seed, 'flame.lmk', (FL.STATIC_LMK,), Fc)
+    sd['lmk_bary_coords'] = _counter_simplex(seed, 'flame.lmk_b', (FL.STATIC_LMK, 3), 0.1)
+    sd['dynamic_lmk_faces_idx'] = _counter_index(seed, 'flame.dyn', (FL.DYN_ROWS, FL.DYN_LMK), Fc)
+    sd['dynamic_lmk_bary_coords'] = _counter_simplex(seed, 'flame.dyn_b', (FL.DYN_ROWS, FL.DYN_LMK, 3), 0.1)
+    sd['full_lmk_faces_idx'] = _counter_index(seed, 'flame.full', (1, FL.LANDMARKS), Fc)
+    sd['full_lmk_bary_coords'] = _counter_simplex(seed, 'flame.full_b', (1, FL.LANDMARKS, 3), 0.1)
+    sd['neck_kin_chain'] = torch.tensor([1, 0], dtype=torch.long)
+    return sd
+
+
+def write_flame_files(state, directory):
+    """Writes a FLAME state as the two files the reference's constructor reads -> (generic_model.pkl, landmark_embedding.npy):
+    shapedirs spread to the 300 / 350 column split of the full model, posedirs as [V,3,36], the dynamic tables as torch tensors."""
+    import os
+    import pickle
+    V = state['v_template'].shape[0]
+    sd = state['shapedirs'].numpy()
+    full = np.zeros((V, 3, 400), dtype=np.float32)
+    full[:, :, :100] = sd[:, :, :100]
+    full[:, :, 300:350] = sd[:, :, 100:]
+    kin = np.zeros((2, 5), dtype=np.int64)
+    kin[0] = [4294967295, 0, 1, 1, 1]
+    kin[1] = np.arange(5)
+    model = {'f': state['faces_tensor'].numpy(), 'v_template': state['v_template'].numpy(), 'shapedirs': full,
+             'posedirs': np.ascontiguousarray(state['posedirs'].numpy().T).reshape(V, 3, -1),
+             'J_regressor': state['J_regressor'].numpy(), 'kintree_table': kin, 'weights': state['lbs_weights'].numpy()}
+    emb = {'static_lmk_faces_idx': state['lmk_faces_idx'].numpy(), 'static_lmk_bary_coords': state['lmk_bary_coords'].numpy(),
+           'dynamic_lmk_faces_idx': state['dynamic_lmk_faces_idx'].clone(), 'dynamic_lmk_bary_coords': state['dynamic_lmk_bary_coords'].clone(),
+           'full_lmk_faces_idx': state['full_lmk_faces_idx'].numpy(), 'full_lmk_bary_coords': state['full_lmk_bary_coords'].numpy()}
+    pkl, npy = os.path.join(directory, 'generic_model.pkl'), os.path.join(directory, 'landmark_embedding.npy')
+    with open(pkl, 'wb') as f:
+        pickle.dump(model, f, protocol=2)
+    np.save(npy, np.array(emb, dtype=object), allow_pickle=True)
+    return pkl, npy
+
+
+def synthetic_flame_coeffs(seed, key, rows, yaw=None):
+    """3DMM coefficient sets shaped like DECA's codedict: shape N(0, 0.8), exp N(0, 0.6), pose N(0, 0.15) with the head's y
+    rotation (column 1) replaced by `yaw` (radians, one per row) when given, cam near (8, 0, 0)."""
+    pose = counter_tensor(seed, key + '.pose', (rows, 6), 0.0, 0.15)
+    if yaw is not None:
+        pose[:, 1] = torch.as_tensor(yaw, dtype=torch.float32)
+    cam = counter_tensor(seed, key + '.cam', (rows, 3), 0.0, 0.05)
+    cam[:, 0] += 8.0
+    return {'shape': counter_tensor(seed, key + '.shape', (rows, 100), 0.0, 0.8), 'exp': counter_tensor(seed, key + '.exp', (rows, 50), 0.0, 0.6),
+            'pose': pose, 'cam': cam}
