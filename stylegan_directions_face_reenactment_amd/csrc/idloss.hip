@@ -643,8 +643,9 @@ extern "C" int64_t sgdfr_idloss_saved_elems(int rows) {
 }
 
 extern "C" int64_t sgdfr_idloss_workspace_bytes(int rows, int H, int W) {
+    // the size does not depend on the window; forward / backward refuse an empty crop window themselves (crop=1 only)
     Window w;
-    if (rows < 1 || rows > 4096 || !make_window(H, W, 1, w) || !make_window(H, W, 0, w)) return -1;
+    if (rows < 1 || rows > 4096 || !make_window(H, W, 0, w)) return -1;
     return ws_layout(rows).total * (int64_t)sizeof(float);
 }
 

@@ -148,11 +148,18 @@ def test_native_symbols_and_error_paths():
     assert lib.sgdfr_idloss_pack_elems() >= 2 * 43_000_000           # forward + input-gradient weights (349 MB)
     assert lib.sgdfr_idloss_saved_elems(2) == 2 * lib.sgdfr_idloss_saved_elems(1) > 0
     assert lib.sgdfr_idloss_saved_elems(0) < 0
-    assert lib.sgdfr_idloss_workspace_bytes(1, 30, 256) < 0          # the crop window [35:223] of 30 rows is empty
+    # the workspace does not depend on the window: 30 rows are fine without the crop (AdaptiveAvgPool2d takes any size) ...
+    assert lib.sgdfr_idloss_workspace_bytes(1, 30, 256) == lib.sgdfr_idloss_workspace_bytes(1, 256, 256) > 0
+    assert lib.sgdfr_idloss_workspace_bytes(1, 0, 256) < 0 and lib.sgdfr_idloss_workspace_bytes(1, 256, 8193) < 0
     assert lib.sgdfr_idloss_workspace_bytes(0, 256, 256) < 0
     one = ctypes.c_void_p(1)
+    # ... while the crop window [35:223] of 30 rows is empty: refused by the forward and the backward, by name
     rc = lib.sgdfr_idloss_forward_f32(one, 1, None, 0, 30, 256, 1, one, one, None, one, 1 << 40, None)
-    assert rc != 0 and b'unsupported image size' in lib.sgdfr_last_error()
+    assert rc != 0 and b'unsupported image size 30x256 (crop=1)' in lib.sgdfr_last_error()
+    rc = lib.sgdfr_idloss_backward_f32(one, one, 1, 256, 32, 1, one, one, one, 1 << 40, None)
+    assert rc != 0 and b'unsupported image size 256x32 (crop=1)' in lib.sgdfr_last_error()
+    rc = lib.sgdfr_idloss_forward_f32(one, 1, None, 0, 30, 256, 0, None, one, None, one, 1 << 40, None)
+    assert rc != 0 and b'null' in lib.sgdfr_last_error()              # crop=0: past the size check, stopped by the null pack
     rc = lib.sgdfr_idloss_forward_f32(one, 1, None, 0, 256, 256, 1, None, one, None, one, 1 << 40, None)
     assert rc != 0 and b'null' in lib.sgdfr_last_error()
     rc = lib.sgdfr_idloss_forward_f32(one, 1, one, 2, 256, 256, 1, one, one, None, one, 1 << 40, None)   # rows_y > rows_x

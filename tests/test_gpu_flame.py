@@ -89,7 +89,7 @@ def _smooth_case(rows, key):
     return c, w
 
 
-@pytest.mark.parametrize('rows', [1, 3, 16, 32])
+@pytest.mark.parametrize('rows', [1, 3, 16, 32, 17, 24, 33, 40])      # partial first chunk, whole chunks, partial chunks after full ones
 def test_decode_backward_matches_fp64_for_smooth_cotangents(rows):
     from stylegan_directions_face_reenactment_amd import flame as FL
     m = _module(SEED)

@@ -135,12 +135,12 @@ def test_stages_and_input_gradient_match_fp64(B, H, W, crop):
         assert _outside_window_nonzero(xg.grad) == 0
 
 
-def test_live_y_cached_target_and_broadcast_agree():
+def _live_cached_broadcast_agree(B):
     m, _ = _module()
-    x = _images('idl.bx', (3, 3, 256, 256)).cuda()
+    x = _images('idl.bx', (B, 3, 256, 256)).cuda()
     y1 = _images('idl.by', (1, 3, 256, 256)).cuda()
     runs = []
-    for y in (y1, m.target(y1), y1.expand(3, -1, -1, -1).contiguous()):
+    for y in (y1, m.target(y1), y1.expand(B, -1, -1, -1).contiguous()):
         xg = x.clone().requires_grad_(True)
         loss = m(xg, y)
         loss.backward()
@@ -148,6 +148,15 @@ def test_live_y_cached_target_and_broadcast_agree():
     for loss, g in runs[1:]:
         assert abs(float(loss) - float(runs[0][0])) <= 1e-5 * abs(float(runs[0][0]))   # target(y) alone: its own split-K plan
         assert _rel(g, runs[0][1]) <= 1e-5
+
+
+def test_live_y_cached_target_and_broadcast_agree():
+    _live_cached_broadcast_agree(3)
+
+
+def test_live_y_cached_target_and_broadcast_agree_at_b16():
+    """At 16 rows most convs keep K in one slice: the rule that x's rows decide the plan holds there as where everything is sliced."""
+    _live_cached_broadcast_agree(16)
 
 
 def test_eager_calls_and_graph_replay_are_bit_identical():
