@@ -652,6 +652,37 @@ int sgdfr_shape_loss_f32(const float* landmarks2d, const float* trans_verts, int
                          float lambda_eye, float* loss, float* terms, float* g_landmarks2d, float* g_trans_verts, void* workspace,
                          int64_t workspace_bytes, void* stream);
 
+/* DECA's coefficient encoder in eval mode (libs/DECA/decalib/models/encoders.py ResnetEncoder(outsize=236), models/resnet.py:21-118,
+ * datasets/datasets.py:57-82, libs/utilities/image_utils.py:87-94, utils/rotation_converter.py:312-360), csrc/deca.hip.
+ * Images x [rows,3,H,W] fp32 in [-1,1] (values beyond are clamped); mat [rows,2,3] maps an output pixel (u, v, 1) of the 224x224 crop
+ * to a source pixel (x, y), sampled bilinearly with zero padding.
+ * sgdfr_deca_prepack_f32: params = host array of 134 device pointers with every BatchNorm folded on the host:
+ *   stem w0 [64,3,7,7], b0 [64]; per bottleneck (16): w1 [P,Cin], b1 [P], w2 [P,P,3,3], b2 [P], w3 [4P,P], b3 [4P], projection
+ *   wd [4P,Cin], bd [4P] (both NULL where the shortcut is the identity); regressor fc1 [1024,2048], [1024], fc2 [236,1024], [236]
+ *   -> pack of sgdfr_deca_pack_elems() floats (forward and input-gradient weights; rebuild it whenever a parameter changes).
+ * sgdfr_deca_forward_f32: crop [rows,3,224,224] in [0,1], params [rows,236], angles [rows,3] = the Euler angles in degrees of
+ *   parameters 200..202.  saved (NULL: nothing is kept) receives sgdfr_deca_saved_elems(rows) bytes: one per ReLU decision and
+ *   max-pool choice.  debug (NULL: off) receives sgdfr_deca_debug_elems(rows) floats: the stem, the pool, each stage's first and
+ *   last bottleneck output and the pooled features, each [rows, ...].
+ * sgdfr_deca_backward_f32: dx [rows,3,H,W] = dL/dx for grad_params [rows,236], from the saved bytes of a forward with the same rows,
+ *   x, mat, H, W and pack.  Exactly zero where |x| > 1.
+ * sgdfr_deca_crop_f32 / sgdfr_deca_crop_backward_f32: the front alone (range map, crop, / 255) and its adjoint to x for a cotangent
+ *   grad_crop [rows,3,224,224].
+ * workspace: device scratch of at least sgdfr_deca_workspace_bytes(rows, H, W) bytes.  The split-K plan follows the row count only.
+ * Deterministic (no float atomics), no host synchronisation, everything on `stream`. */
+int64_t sgdfr_deca_pack_elems(void);
+int64_t sgdfr_deca_saved_elems(int rows);
+int64_t sgdfr_deca_debug_elems(int rows);
+int64_t sgdfr_deca_workspace_bytes(int rows, int H, int W);
+int sgdfr_deca_prepack_f32(const float* const* params, float* pack, void* stream);
+int sgdfr_deca_crop_f32(const float* x, const float* mat, int rows, int H, int W, float* crop, void* stream);
+int sgdfr_deca_crop_backward_f32(const float* grad_crop, const float* x, const float* mat, int rows, int H, int W, float* dx,
+                                 void* stream);
+int sgdfr_deca_forward_f32(const float* x, const float* mat, int rows, int H, int W, const float* pack, float* crop, float* params,
+                           float* angles, uint8_t* saved, float* debug, void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_deca_backward_f32(const float* grad_params, const float* x, const float* mat, const uint8_t* saved, int rows, int H, int W,
+                            const float* pack, float* dx, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

@@ -177,6 +177,14 @@ SIGNATURES['sgdfr_flame_decode_backward_f32'] = [_c_f32p, _c_f32p, _c_f32p, _c_f
 SIGNATURES['sgdfr_shape_loss_f32'] = [_c_f32p, _c_f32p, _i, _f, _f, _f, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64,
                                       ctypes.c_void_p]
 FLAME_PARAMS = 15       # pointers sgdfr_flame_prepack_f32 takes
+SIGNATURES['sgdfr_deca_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_deca_forward_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p,
+                                        ctypes.c_void_p, _i64, ctypes.c_void_p]
+SIGNATURES['sgdfr_deca_backward_f32'] = [_c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i, _i, _i, _c_f32p, _c_f32p, ctypes.c_void_p, _i64,
+                                         ctypes.c_void_p]
+SIGNATURES['sgdfr_deca_crop_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_deca_crop_backward_f32'] = [_c_f32p, _c_f32p, _c_f32p, _i, _i, _i, _c_f32p, ctypes.c_void_p]
+DECA_PARAMS = 134       # pointers sgdfr_deca_prepack_f32 takes
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
 OPTIONAL_SIGNATURES = {'sgdfr_mfma_ceiling_probe': [_i, _i, _i, _i, _i, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]}
@@ -222,6 +230,13 @@ def load():
     for name in ('sgdfr_flame_saved_elems', 'sgdfr_flame_workspace_bytes'):
         getattr(lib, name).argtypes = [ctypes.c_int]
         getattr(lib, name).restype = ctypes.c_int64
+    lib.sgdfr_deca_pack_elems.argtypes = []
+    lib.sgdfr_deca_pack_elems.restype = ctypes.c_int64
+    for name in ('sgdfr_deca_saved_elems', 'sgdfr_deca_debug_elems'):
+        getattr(lib, name).argtypes = [ctypes.c_int]
+        getattr(lib, name).restype = ctypes.c_int64
+    lib.sgdfr_deca_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.sgdfr_deca_workspace_bytes.restype = ctypes.c_int64
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():

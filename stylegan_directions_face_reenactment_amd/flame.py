@@ -9,7 +9,7 @@ libs/utilities/utils_train.py:383-419 with libs/criteria/losses.py.
 
 Everything from the coefficients to the loss and back runs in seven launches (pose, vertices, landmarks, loss, sum; vertex backward,
 pose backward) without a host synchronisation, so it captures into a graph; results are bit-identical from call to call.  The
-coefficient encoder (DECA's ResNet-50) stays with the caller.  The joint regressor is folded into the blend-shape basis on the host in
+coefficient encoder (DECA's ResNet-50) is deca.py: deca.encode's dict feeds decode / ShapeLoss directly.  The joint regressor is folded into the blend-shape basis on the host in
 fp64 (J = J_regressor v_template + (J_regressor shapedirs) betas), once per buffer version; the device pack is rebuilt whenever a
 buffer's storage or version changes.
 """

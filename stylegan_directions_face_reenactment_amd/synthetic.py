@@ -235,6 +235,37 @@ def synthetic_arcface_state(seed):
     return out
 
 
+def synthetic_deca_encoder_state(seed):
+    """Seeded DECA coefficient-encoder state dict in encoders.ResnetEncoder(outsize=236)'s keys (deca.ResnetEncoder): He-scaled
+    conv filters N(0, 2/fan_in), BatchNorm statistics near (0, 1), the scale of each bottleneck's last BatchNorm (bn3) and of the
+    projection's around 0.5 -- so the residual sums stay O(1) through the 16 bottlenecks --, Linear weights N(0, 1/fan_in) with
+    small biases.  103 MB: regenerated from the seed wherever it is needed, never stored."""
+    from collections import OrderedDict
+    from .deca import ResnetEncoder
+    out = OrderedDict()
+    for key, t in ResnetEncoder().state_dict().items():
+        shape = tuple(t.shape)
+        if key.endswith('num_batches_tracked'):
+            out[key] = torch.zeros(shape, dtype=torch.int64)
+        elif key.endswith('running_var'):
+            v = counter_normal(seed, key, int(np.prod(shape))) * 0.2 + 1.0
+            out[key] = torch.from_numpy(np.maximum(v, 0.3).astype(np.float32).reshape(shape))
+        elif key.endswith('running_mean'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.1)
+        elif len(shape) == 4:
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))))
+        elif len(shape) == 2:
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(1.0 / shape[1])))
+        elif key.endswith('.bias'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.05)
+        elif key.endswith('.weight'):                             # BatchNorm scale
+            last = '.bn3.' in key or '.downsample.1.' in key
+            out[key] = counter_tensor(seed, key, shape, 0.5 if last else 1.0, 0.05 if last else 0.1)
+        else:
+            raise KeyError(key)
+    return out
+
+
 def _counter_index(seed, key, shape, n):
     """Integers in 0..n-1 from the counter generator."""
     count = int(np.prod(shape))

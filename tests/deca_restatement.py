@@ -1,0 +1,218 @@
+"""Plain-torch restatement of DECA's coefficient encoder path (stylegan_directions_face_reenactment_amd/deca.py, csrc/deca.hip):
+range map + affine crop by F.grid_sample, the ResNet-50 trunk with BatchNorm unfolded (eval statistics) or folded, the regressor,
+the split of the 236 parameters and the Euler angles.  Runs in any dtype on any device (fp64 on the CPU for the fixture checks,
+fp32 on the GPU as the stock module).  `encoder` returns every pre-activation, and takes optional decision masks: with them each
+ReLU becomes a multiplication by the given 0/1 mask and the max-pool a gather of the given choices, so that autograd gives the
+gradient under exactly those decisions."""
+import math
+
+import torch
+import torch.nn.functional as F
+
+LAYERS = ((64, 3), (128, 4), (256, 6), (512, 3))
+CROP = 224
+
+
+def block_names():
+    return ['layer%d.%d' % (i + 1, k) for i, (_, n) in enumerate(LAYERS) for k in range(n)]
+
+
+def front(x, M):
+    """[-1,1] images -> [0,255] -> bilinear sample (zero padding) at (u, v, 1) M^T for the 224x224 output pixels -> / 255."""
+    B, _, H, W = x.shape
+    v = (x.clamp(-1, 1) + 1) / (2 + 1e-5) * 255.0
+    u = torch.arange(CROP, dtype=x.dtype, device=x.device)
+    vv, uu = torch.meshgrid(u, u, indexing='ij')
+    M = M.to(x.dtype)
+    sx = M[:, 0, 0].view(B, 1, 1) * uu + M[:, 0, 1].view(B, 1, 1) * vv + M[:, 0, 2].view(B, 1, 1)
+    sy = M[:, 1, 0].view(B, 1, 1) * uu + M[:, 1, 1].view(B, 1, 1) * vv + M[:, 1, 2].view(B, 1, 1)
+    grid = torch.stack([2 * sx / (W - 1) - 1, 2 * sy / (H - 1) - 1], -1)
+    return F.grid_sample(v, grid, mode='bilinear', padding_mode='zeros', align_corners=True) / 255.0
+
+
+def _relu(pre, mask):
+    return torch.relu(pre) if mask is None else pre * mask.to(pre.dtype)
+
+
+def pool_choice(stem):
+    """max_pool2d(3, 2, 1) -> (pooled, choice kh*3 + kw of the winner, the first maximum in row-major order)."""
+    pooled, idx = F.max_pool2d(stem, 3, 2, 1, return_indices=True)
+    Hs = stem.shape[-1]
+    y, x = idx // Hs, idx % Hs
+    i = torch.arange(pooled.shape[-2], device=stem.device).view(1, 1, -1, 1)
+    j = torch.arange(pooled.shape[-1], device=stem.device).view(1, 1, 1, -1)
+    return pooled, (y - (2 * i - 1)) * 3 + (x - (2 * j - 1))
+
+
+def _pool_given(stem, arg):
+    B, C, Hs, Ws = stem.shape
+    p = F.pad(stem, (1, 1, 1, 1), value=0.0)               # a padded tap is never a recorded choice
+    patches = F.unfold(p, 3, stride=2).view(B, C, 9, -1)
+    out = patches.gather(2, arg.reshape(B, C, 1, -1).long())
+    return out.view(B, C, Hs // 2, Ws // 2)
+
+
+def encoder(sd, crop, fold=False, masks=None):
+    """sd: the ResnetEncoder state dict (any dtype; converted to crop's).  masks: None, or {'stem', 'arg', 'm1': [16], 'm2': [16],
+    'm3': [16], 'fc'}.  Returns a dict: stem_pre, stem, pool, arg, per block pre1 / pre2 / pre3 / out (lists of 16), feat, fc_pre,
+    params."""
+    dt, dev = crop.dtype, crop.device
+    g = lambda k: sd[k].to(device=dev, dtype=dt)
+
+    def conv_bn(x, conv, bn, stride=1, padding=0):
+        w = g(conv + '.weight')
+        if fold:
+            s = g(bn + '.weight') * torch.rsqrt(g(bn + '.running_var') + 1e-5)
+            return F.conv2d(x, w * s.view(-1, 1, 1, 1), g(bn + '.bias') - g(bn + '.running_mean') * s, stride, padding)
+        y = F.conv2d(x, w, None, stride, padding)
+        return F.batch_norm(y, g(bn + '.running_mean'), g(bn + '.running_var'), g(bn + '.weight'), g(bn + '.bias'), False, 0.0, 1e-5)
+
+    m = masks or {}
+    rec = {'pre1': [], 'pre2': [], 'pre3': [], 'out': []}
+    rec['stem_pre'] = conv_bn(crop, 'encoder.conv1', 'encoder.bn1', 2, 3)
+    rec['stem'] = _relu(rec['stem_pre'], m.get('stem'))
+    if masks is None:
+        rec['pool'], rec['arg'] = pool_choice(rec['stem'])
+    else:
+        rec['pool'], rec['arg'] = _pool_given(rec['stem'], m['arg']), m['arg']
+    x = rec['pool']
+    for n, name in enumerate(block_names()):
+        p = 'encoder.' + name
+        stride = 2 if (name.endswith('.0') and not name.startswith('layer1')) else 1
+        pre1 = conv_bn(x, p + '.conv1', p + '.bn1')
+        a1 = _relu(pre1, m['m1'][n] if masks else None)
+        pre2 = conv_bn(a1, p + '.conv2', p + '.bn2', stride, 1)
+        a2 = _relu(pre2, m['m2'][n] if masks else None)
+        res = conv_bn(x, p + '.downsample.0', p + '.downsample.1', stride) if name.endswith('.0') else x
+        pre3 = conv_bn(a2, p + '.conv3', p + '.bn3') + res
+        x = _relu(pre3, m['m3'][n] if masks else None)
+        rec['pre1'].append(pre1), rec['pre2'].append(pre2), rec['pre3'].append(pre3), rec['out'].append(x)
+    rec['feat'] = F.avg_pool2d(x, 7, 1).flatten(1)
+    rec['fc_pre'] = F.linear(rec['feat'], g('layers.0.weight'), g('layers.0.bias'))
+    h = _relu(rec['fc_pre'], m.get('fc'))
+    rec['params'] = F.linear(h, g('layers.2.weight'), g('layers.2.bias'))
+    return rec
+
+
+def relu_decisions(rec):
+    """Every ReLU pre-activation of a record, in the order of deca.saved_views: stem, then m1, m2, m3 per block, then fc."""
+    out = [rec['stem_pre']]
+    for a, b, c in zip(rec['pre1'], rec['pre2'], rec['pre3']):
+        out += [a, b, c]
+    return out + [rec['fc_pre']]
+
+
+def angles(pose3):
+    """rad2deg(batch_axis2euler(pose[:, :3])) for every row: axis-angle -> quaternion -> rotation matrix -> Euler (x, y, z);
+    beyond |R20| > 0.998: z = 0, x = +-pi/2, y = atan2(-+R01, -+R02)."""
+    a0, a1, a2 = pose3.unbind(1)
+    t2 = a0 * a0 + a1 * a1 + a2 * a2
+    th = torch.sqrt(t2)
+    nz = t2 > 0
+    safe = torch.where(nz, th, torch.ones_like(th))
+    k = torch.where(nz, torch.sin(0.5 * safe) / safe, torch.full_like(th, 0.5))
+    w = torch.where(nz, torch.cos(0.5 * th), torch.ones_like(th))
+    q = torch.stack([w, a0 * k, a1 * k, a2 * k], 1)
+    q = q / q.norm(p=2, dim=1, keepdim=True)
+    w, x, y, z = q.unbind(1)
+    r00, r01, r02 = w * w + x * x - y * y - z * z, 2 * x * y - 2 * w * z, 2 * w * y + 2 * x * z
+    r10 = 2 * w * z + 2 * x * y
+    r20, r21, r22 = 2 * x * z - 2 * w * y, 2 * w * x + 2 * y * z, w * w - x * x - y * y + z * z
+    ex = torch.asin(r20.clamp(-1, 1))
+    c = torch.cos(ex)
+    ey, ez = torch.atan2(r21 / c, r22 / c), torch.atan2(r10 / c, r00 / c)
+    hi, lo = r20 > 0.998, r20 < -0.998
+    half = torch.full_like(ex, math.pi / 2)
+    ex = torch.where(hi, half, torch.where(lo, -half, ex))
+    ey = torch.where(hi, torch.atan2(-r01, -r02), torch.where(lo, torch.atan2(r01, r02), ey))
+    ez = torch.where(hi | lo, torch.zeros_like(ez), ez)
+    return 180.0 * torch.stack([ex, ey, ez], 1) / math.pi
+
+
+def run(sd, x, M, fold=False, masks=None):
+    """The whole path -> record of `encoder` plus 'crop' and 'angles'."""
+    crop = front(x, M)
+    rec = encoder(sd, crop, fold, masks)
+    rec['crop'] = crop
+    rec['angles'] = angles(rec['params'][:, 200:203].detach())
+    return rec
+
+
+# ---------------------------------------------------------------------------------------------------------------- crop restatement
+def similarity_fit(src, dst):
+    """Least-squares similarity transform (Umeyama 1991) src -> dst for [n,2] point sets, as a 3x3 matrix: what
+    skimage.transform.estimate_transform('similarity', src, dst).params holds."""
+    import numpy as np
+    src, dst = np.asarray(src, dtype=np.float64), np.asarray(dst, dtype=np.float64)
+    n, d = src.shape
+    ms, md = src.mean(0), dst.mean(0)
+    sc, dc = src - ms, dst - md
+    A = dc.T @ sc / n
+    dv = np.ones(d)
+    if np.linalg.det(A) < 0:
+        dv[d - 1] = -1
+    U, Sg, Vt = np.linalg.svd(A)
+    R = U @ np.diag(dv) @ Vt
+    scale = (Sg @ dv) / sc.var(0).sum()
+    T = np.eye(d + 1)
+    T[:d, :d] = scale * R
+    T[:d, d] = md - scale * (R @ ms)
+    return T
+
+
+def box_transform(box, scale=1.25, crop=CROP):
+    """TestData.get_image_tensor's transform for one 'kpt68' box [left, top, right, bottom]: bbox2point, size = int(old_size * scale),
+    the similarity fit through the three corner points -> 3x3 (source pixel -> crop pixel)."""
+    import numpy as np
+    left, top, right, bottom = [float(v) for v in box]
+    old_size = (right - left + bottom - top) / 2 * 1.1
+    center = np.array([right - (right - left) / 2.0, bottom - (bottom - top) / 2.0])
+    size = int(old_size * scale)
+    src = np.array([[center[0] - size / 2, center[1] - size / 2], [center[0] - size / 2, center[1] + size / 2],
+                    [center[0] + size / 2, center[1] - size / 2]])
+    dst = np.array([[0, 0], [0, crop - 1], [crop - 1, 0]])
+    return similarity_fit(src, dst)
+
+
+def warp_affine_composed(src, theta, dsize=(CROP, CROP), align_corners=False):
+    """kornia 0.4.1's warp_affine as remembered (no copy of kornia was at hand: this composition is unverified against it):
+    normalise the source and destination pixel grids with normal_transform_pixel (2 / (size - 1), -1), invert, F.affine_grid +
+    F.grid_sample(bilinear, zeros).  theta [B,2,3]: source pixel -> destination pixel."""
+    B, C, H, W = src.shape
+
+    def normal(h, w):
+        return torch.tensor([[2.0 / (w - 1), 0, -1], [0, 2.0 / (h - 1), -1], [0, 0, 1]], dtype=src.dtype, device=src.device)
+
+    M3 = torch.eye(3, dtype=src.dtype, device=src.device).repeat(B, 1, 1)
+    M3[:, :2] = theta.to(src.dtype)
+    dst_norm_trans_src_norm = normal(*dsize) @ M3 @ torch.inverse(normal(H, W))
+    src_norm_trans_dst_norm = torch.inverse(dst_norm_trans_src_norm)
+    grid = F.affine_grid(src_norm_trans_dst_norm[:, :2], [B, C, dsize[0], dsize[1]], align_corners=align_corners)
+    return F.grid_sample(src, grid, mode='bilinear', padding_mode='zeros', align_corners=align_corners)
+
+
+# ---------------------------------------------------------------------------------------------------------------- kat12 inputs
+# name -> (image shape, 'kpt68' boxes): B=1 at 256^2 with a box partly outside the image; B=2 at 200x300 (H x W), row 1 with values
+# beyond +-1
+CASES = {'a': ((1, 3, 256, 256), [[60.0, 80.0, 290.0, 300.0]]),
+         'b': ((2, 3, 200, 300), [[70.0, 40.0, 230.0, 180.0], [20.0, 30.0, 180.0, 170.0]])}
+WINDOW = 128
+
+
+def fixture_inputs(S, seed, name):
+    """The fixture's images, boxes and dL/dparameters, regenerated from the seed (the npz stores only the keys)."""
+    shape, boxes = CASES[name]
+    x = S.counter_tensor(seed, 'kat12.x.' + name, shape, 0.0, 0.5)
+    if name == 'b':
+        x[0].clamp_(-1, 1)
+        x[1] *= 1.6
+    else:
+        x.clamp_(-1, 1)
+    g = S.counter_tensor(seed, 'kat12.g.' + name, (shape[0], 236), 0.0, 1.0)
+    return x, torch.tensor(boxes, dtype=torch.float64), g
+
+
+def window(name):
+    """The 128 x 128 window of row 0 whose dL/dx the fixture stores (centred)."""
+    _, _, H, W = CASES[name][0]
+    return slice((H - WINDOW) // 2, (H + WINDOW) // 2), slice((W - WINDOW) // 2, (W + WINDOW) // 2)
