@@ -683,6 +683,40 @@ int sgdfr_deca_forward_f32(const float* x, const float* mat, int rows, int H, in
 int sgdfr_deca_backward_f32(const float* grad_params, const float* x, const float* mat, const uint8_t* saved, int rows, int H, int W,
                             const float* pack, float* dx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The 2D-FAN-4 landmark detector in eval mode (libs/face_models/fan_model/models.py:145-202 FAN(4), landmarks_estimation.py:50-88 and
+ * :143-185, fan_model/utils.py:63-97 and :140-165, libs/DECA/decalib/datasets/detectors.py:38-41), csrc/fan.hip.  Forward only.
+ * Images x [rows,3,H,W] fp32, 0..255 (SGDFR_FAN_RANGE_255) or [-1,1] mapped to 0..255 as torch_range_1_to_255 does
+ * (SGDFR_FAN_RANGE_GAN); faces [rows,4] fp32 on the device: x0, y0, x1, y1 of the face box.  Centre, scale and the integer window are
+ * computed on the device in float32 in the reference's order of operations.
+ * sgdfr_fan_prepack_f32: params = host array of 735 device pointers, BatchNorms folded on the host to (g, h) = (w rsqrt(var + eps),
+ *   b - mean g):  stem w0 [64,3,7,7] and b0 [64] with bn1 folded in;  per ConvBlock (59: conv2, conv3, conv4, then per stack
+ *   b1_4 b2_4 b3_4 b1_3 ... b3_1 b2_plus_1 top_m) g1 h1 w1 g2 h2 w2 g3 h3 w3 and the projection's gd hd wd (NULL where in == out);
+ *   per stack conv_last w [256,256], b [256] with bn_end folded in, l w [68,256], b [68];  per stack but the last bl w [256,256],
+ *   al w [256,68], bl b + al b [256]  -> pack of sgdfr_fan_pack_elems() floats (rebuild it whenever a parameter changes).
+ * sgdfr_fan_crop_f32: the front alone -> crop [rows,3,256,256] in [0,1].
+ * sgdfr_fan_network_f32: crop -> the last stack's heatmaps [rows,68,64,64].  debug (NULL: off) receives sgdfr_fan_debug_elems(rows)
+ *   floats: the stem [rows,64,128,128], conv4's output [rows,256,64,64], then per stack the hourglass output [rows,256,64,64] and
+ *   the heatmaps [rows,68,64,64].
+ * sgdfr_fan_decode_f32: heatmaps -> pts [rows,68,2] (crop pixels), pts_img [rows,68,2] (image pixels, integer-valued) and, when boxes
+ *   is not NULL, boxes [rows,4] = min x, min y, max x, max y of pts_img.  sgdfr_fan_boxes_f32: the boxes of any [rows,68,2] points.
+ * sgdfr_fan_forward_f32: crop + network + decode in one call.
+ * workspace: device scratch of at least sgdfr_fan_workspace_bytes(rows, H, W) bytes.  The split-K plan follows the row count only.
+ * Deterministic (no float atomics), no host synchronisation, everything on `stream`. */
+#define SGDFR_FAN_RANGE_255 0
+#define SGDFR_FAN_RANGE_GAN 1
+int64_t sgdfr_fan_pack_elems(void);
+int64_t sgdfr_fan_debug_elems(int rows);
+int64_t sgdfr_fan_workspace_bytes(int rows, int H, int W);
+int sgdfr_fan_prepack_f32(const float* const* params, float* pack, void* stream);
+int sgdfr_fan_crop_f32(const float* x, const float* faces, int rows, int H, int W, int input_range, float* crop, void* stream);
+int sgdfr_fan_network_f32(const float* crop, int rows, const float* pack, float* heatmaps, float* debug, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int sgdfr_fan_decode_f32(const float* heatmaps, const float* faces, int rows, float* pts, float* pts_img, float* boxes, void* stream);
+int sgdfr_fan_boxes_f32(const float* pts_img, int rows, float* boxes, void* stream);
+int sgdfr_fan_forward_f32(const float* x, const float* faces, int rows, int H, int W, int input_range, const float* pack,
+                          float* heatmaps, float* pts, float* pts_img, float* boxes, float* debug, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

@@ -185,6 +185,15 @@ SIGNATURES['sgdfr_deca_backward_f32'] = [_c_f32p, _c_f32p, _c_f32p, ctypes.c_voi
 SIGNATURES['sgdfr_deca_crop_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _c_f32p, ctypes.c_void_p]
 SIGNATURES['sgdfr_deca_crop_backward_f32'] = [_c_f32p, _c_f32p, _c_f32p, _i, _i, _i, _c_f32p, ctypes.c_void_p]
 DECA_PARAMS = 134       # pointers sgdfr_deca_prepack_f32 takes
+SIGNATURES['sgdfr_fan_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_fan_crop_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_fan_network_f32'] = [_c_f32p, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+SIGNATURES['sgdfr_fan_decode_f32'] = [_c_f32p, _c_f32p, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_fan_boxes_f32'] = [_c_f32p, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_fan_forward_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _i, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                       ctypes.c_void_p, _i64, ctypes.c_void_p]
+FAN_PARAMS = 735        # pointers sgdfr_fan_prepack_f32 takes
+FAN_RANGE_255, FAN_RANGE_GAN = 0, 1      # include/sgdfr.h SGDFR_FAN_RANGE_*
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
 OPTIONAL_SIGNATURES = {'sgdfr_mfma_ceiling_probe': [_i, _i, _i, _i, _i, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]}
@@ -237,6 +246,12 @@ def load():
         getattr(lib, name).restype = ctypes.c_int64
     lib.sgdfr_deca_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.sgdfr_deca_workspace_bytes.restype = ctypes.c_int64
+    lib.sgdfr_fan_pack_elems.argtypes = []
+    lib.sgdfr_fan_pack_elems.restype = ctypes.c_int64
+    lib.sgdfr_fan_debug_elems.argtypes = [ctypes.c_int]
+    lib.sgdfr_fan_debug_elems.restype = ctypes.c_int64
+    lib.sgdfr_fan_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.sgdfr_fan_workspace_bytes.restype = ctypes.c_int64
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():

@@ -8,7 +8,9 @@ Only the modules of the hot path are aliased; everything else u
 resolving to the reference checkout on sys.path.  ``install_lpips(state_dict)`` (opt-in) additionally mounts the HIP LPIPS at
 ``libs.criteria.lpips.lpips`` so that unchanged ``LPIPS(net_type='alex')`` calls get it with those weights (no torchvision, no
 download); ``install_id_loss(path)`` (opt-in) mounts the HIP identity loss at ``libs.criteria.id_loss`` the same way.
-``libs.utilities.generic`` is NOT replaced wholesale
+There is no ``install_landmarks``: ``LandmarksEstimation`` (libs/face_models/landmarks_estimation.py) owns the S3FD face detector as
+well as the FAN network, and mounting half a class helps nobody; call ``landmarks.get_landmarks`` with the detector's boxes instead
+(INTEGRATION.md).  ``libs.utilities.generic`` is NOT replaced wholesale
 (it also holds DECA glue); call ``patch_generic(module)`` to swap in the two fused functions.
 """
 import importlib

@@ -14,7 +14,8 @@ reference encodes one row at a time.  The parameters are differentiable to the i
 `images` are marked non-differentiable: no caller differentiates them.  Nothing is saved for a backward under torch.no_grad() or
 when the images need no gradient.  All 53 BatchNorms are folded into filters + bias on the host in fp64, once per weight
 version; the device pack (forward and input-gradient weights, ~2 x 102 MB) is rebuilt whenever a parameter's storage or version
-changes.  The face detector stays with the caller: boxes come in as numbers, and a row the detector failed on is the caller's
+changes.  The 'kpt68' boxes come in as numbers: landmarks.get_landmarks -> landmarks.kpt68_boxes computes them on the device from the
+caller's face boxes (the S3FD face detector itself stays with the caller), and a row the detector failed on is the caller's
 business (the reference zeroes its coefficients and sets its angles to -180).  E_detail is not built.
 """
 import ctypes

@@ -1,0 +1,340 @@
+"""The 2D-FAN-4 landmark detector on the HIP kernels of csrc/fan.hip: the counterpart of libs/face_models/fan_model/models.py
+FAN(4), of LandmarksEstimation.get_landmarks (landmarks_estimation.py:143-185, 2D branch, flip_input=False) with crop_torch and
+transform (fan_model/utils.py:63-97, 140-165) and get_preds_fromhm (landmarks_estimation.py:50-88), and of the 'kpt68' box of
+libs/DECA/decalib/datasets/detectors.py:38-41 that deca.crop_matrix takes.
+
+    fan = FAN(4); fan.load_state_dict(sd); fan = fan.cuda().eval()          # 2DFAN4-*.pth.tar loads unchanged
+    pts_img, pts, heatmaps = get_landmarks(fan, images, faces, input_range='255')
+    boxes = kpt68_boxes(pts_img)                                            # [B,4] left, top, right, bottom -> deca.crop_matrix
+
+`FAN` has the module layout and the 1129 state-dict keys of the reference's and holds the weights only, frozen at construction;
+the HIP kernels run it in eval mode (running BatchNorm statistics), forward only: the box is a number, nothing differentiates it.
+The whole batch runs in one pass (the reference crops, runs and decodes one face at a time and moves the heatmaps to the CPU and
+back); centre, scale and the integer window are computed on the device, so nothing in a call synchronises with the host.  The
+BatchNorms in front of the ConvBlock convs cannot be folded into filters (a ReLU sits between): they are folded on the host in fp64
+to a per-channel (g, h) that the conv's loader applies; only conv1 + bn1 and conv_last + bn_end fold into filters.  The device pack
+(~95 MB) is rebuilt whenever a parameter's storage or version changes.
+
+The crop: `transforms.Resize` on a tensor is F.interpolate(mode='bilinear', align_corners=False) without antialiasing in the
+torchvision the reference was written for.  torchvision was not available when this was written, so the resize is pinned only
+against F.interpolate composed that way: the composition itself is UNVERIFIED against torchvision.
+
+The S3FD face detector stays with the caller: face boxes come in as numbers.  The 3D landmark type (ResNetDepth) and flip_input are
+not built.
+"""
+import ctypes
+from collections import OrderedDict
+
+import torch
+from torch import nn
+
+from . import _native as N
+
+STACKS = 4
+DEPTH = 4
+POINTS = 68
+CROP = 256
+MAP = 64
+RANGES = {'255': N.FAN_RANGE_255, 'gan': N.FAN_RANGE_GAN}
+
+
+class _ConvBlock(nn.Module):
+    """models.py ConvBlock(in, out): BN -> ReLU -> conv3x3 three times, concatenated, plus the (projected) input.  Weights only."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.bn1 = nn.BatchNorm2d(cin)
+        self.conv1 = nn.Conv2d(cin, cout // 2, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout // 2)
+        self.conv2 = nn.Conv2d(cout // 2, cout // 4, 3, padding=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(cout // 4)
+        self.conv3 = nn.Conv2d(cout // 4, cout // 4, 3, padding=1, bias=False)
+        self.downsample = None
+        if cin != cout:
+            self.downsample = nn.Sequential(nn.BatchNorm2d(cin), nn.ReLU(True), nn.Conv2d(cin, cout, 1, bias=False))
+
+
+class _HourGlass(nn.Module):
+    """models.py HourGlass(1, 4, 256): b1, b2 per level going down, b2_plus at the bottom, b3 per level coming up.  Weights only."""
+
+    def __init__(self, depth, features):
+        super().__init__()
+        self._add(depth, features)
+
+    def _add(self, level, f):
+        self.add_module('b1_%d' % level, _ConvBlock(f, f))
+        self.add_module('b2_%d' % level, _ConvBlock(f, f))
+        if level > 1:
+            self._add(level - 1, f)
+        else:
+            self.add_module('b2_plus_%d' % level, _ConvBlock(f, f))
+        self.add_module('b3_%d' % level, _ConvBlock(f, f))
+
+
+class FAN(nn.Module):
+    """models.FAN(num_modules=4): weights only.  forward(crop [B,3,256,256] in [0,1]) -> the last stack's heatmaps [B,68,64,64]."""
+
+    def __init__(self, num_modules=4):
+        if num_modules != STACKS:
+            raise NotImplementedError('FAN: only num_modules=4 (NetworkSize.LARGE, 2DFAN-4) has HIP kernels, got %r' % (num_modules,))
+        super().__init__()
+        self.num_modules = num_modules
+        self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.conv2 = _ConvBlock(64, 128)
+        self.conv3 = _ConvBlock(128, 128)
+        self.conv4 = _ConvBlock(128, 256)
+        for i in range(num_modules):
+            self.add_module('m%d' % i, _HourGlass(DEPTH, 256))
+            self.add_module('top_m_%d' % i, _ConvBlock(256, 256))
+            self.add_module('conv_last%d' % i, nn.Conv2d(256, 256, 1))
+            self.add_module('bn_end%d' % i, nn.BatchNorm2d(256))
+            self.add_module('l%d' % i, nn.Conv2d(256, POINTS, 1))
+            if i < num_modules - 1:
+                self.add_module('bl%d' % i, nn.Conv2d(256, 256, 1))
+                self.add_module('al%d' % i, nn.Conv2d(POINTS, 256, 1))
+        for p in self.parameters():
+            p.requires_grad = False
+        self._pack = None
+
+    # ---- weights
+    def _key(self):
+        return tuple((t.data_ptr(), t._version, t.device) for t in self.state_dict(keep_vars=True).values())
+
+    def invalidate_packs(self):
+        """Drop the weight pack (needed only after in-place writes through `.data`, which bump no version counter)."""
+        self._pack = None
+
+    def blocks(self):
+        """The 59 ConvBlocks in the order sgdfr_fan_prepack_f32 takes them."""
+        out = [self.conv2, self.conv3, self.conv4]
+        for i in range(STACKS):
+            m = getattr(self, 'm%d' % i)
+            for level in range(DEPTH, 0, -1):
+                out += [getattr(m, 'b%d_%d' % (k, level)) for k in (1, 2, 3)]
+            out += [m.b2_plus_1, getattr(self, 'top_m_%d' % i)]
+        return out
+
+    def folded(self, dtype=torch.float32):
+        """The 735 tensors sgdfr_fan_prepack_f32 takes (None for the projection of an identity block), every BatchNorm folded in
+        fp64 on the parameters' device, returned in `dtype`."""
+        def gh(bn):
+            g = bn.weight.detach().double() * torch.rsqrt(bn.running_var.detach().double() + bn.eps)
+            return g, bn.bias.detach().double() - bn.running_mean.detach().double() * g
+
+        def fold(conv, bn):
+            g, h = gh(bn)
+            return conv.weight.detach().double() * g.view(-1, 1, 1, 1), conv.bias.detach().double() * g + h
+
+        out = list(fold(self.conv1, self.bn1))
+        for b in self.blocks():
+            for bn, conv in ((b.bn1, b.conv1), (b.bn2, b.conv2), (b.bn3, b.conv3)):
+                out += list(gh(bn)) + [conv.weight.detach().double()]
+            if b.downsample is not None:
+                out += list(gh(b.downsample[0])) + [b.downsample[2].weight.detach().double().flatten(1)]
+            else:
+                out += [None, None, None]
+        for i in range(STACKS):
+            w, bias = fold(getattr(self, 'conv_last%d' % i), getattr(self, 'bn_end%d' % i))
+            l = getattr(self, 'l%d' % i)
+            out += [w.flatten(1), bias, l.weight.detach().double().flatten(1), l.bias.detach().double()]
+        for i in range(STACKS - 1):
+            bl, al = getattr(self, 'bl%d' % i), getattr(self, 'al%d' % i)
+            out += [bl.weight.detach().double().flatten(1), al.weight.detach().double().flatten(1),
+                    bl.bias.detach().double() + al.bias.detach().double()]
+        return [None if v is None else v.to(dtype).contiguous() for v in out]
+
+    def packed(self):
+        """The device weight pack of sgdfr_fan_prepack_f32, rebuilt when any parameter's or buffer's storage or version changes."""
+        key = self._key()
+        if self._pack is None or self._pack[0] != key:
+            ps = self.folded()
+            for p in ps:
+                N.require_device(p)
+            dev = self.conv1.weight.device
+            pack = torch.empty(N.load().sgdfr_fan_pack_elems(), dtype=torch.float32, device=dev)
+            arr = (ctypes.c_void_p * N.FAN_PARAMS)(*[None if p is None else p.data_ptr() for p in ps])
+            N.call('sgdfr_fan_prepack_f32', arr, N.ptr(pack), N.stream())
+            self._pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
+        return self._pack[1]
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self.invalidate_packs()
+        return out
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        res = super().load_state_dict(OrderedDict(state_dict), strict=strict, **kwargs)
+        self.invalidate_packs()
+        return res
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state['_pack'] = None
+        return state
+
+    def check(self):
+        if self.training:
+            raise RuntimeError('FAN: the HIP kernels run the network in eval mode only (running BatchNorm statistics); call .eval()')
+        if any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError('FAN: the HIP kernels are forward only and give no gradient for the weights; keep every parameter at '
+                               'requires_grad=False')
+
+    def forward(self, crop):
+        return network(self, crop)
+
+
+# ---------------------------------------------------------------------------------------------------------------- checks
+def _faces(faces, images):
+    """[B,4] float32 x0, y0, x1, y1 on the images' device from a [B,4] / [B,5] tensor or numbers (a fifth column, the score, is
+    dropped).  A device tensor stays on the device."""
+    f = faces if torch.is_tensor(faces) else torch.as_tensor(faces, dtype=torch.float32)
+    if f.dim() != 2 or f.shape[1] not in (4, 5) or f.shape[0] != images.shape[0]:
+        raise ValueError('landmarks: expected [%d,4] (or [%d,5]) face boxes x0, y0, x1, y1, got %s' % (images.shape[0], images.shape[0],
+                                                                                                      tuple(f.shape)))
+    return f
+
+
+def _check_images(images):
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+        raise ValueError('landmarks: expected [B,3,H,W] images, got %s' % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
+
+
+def _range(input_range):
+    if input_range not in RANGES:
+        raise ValueError("landmarks: input_range must be '255' (0..255 values) or 'gan' ([-1,1]), got %r" % (input_range,))
+    return RANGES[input_range]
+
+
+def _prepare(images, faces, input_range):
+    code = _range(input_range)
+    _check_images(images)
+    f = _faces(faces, images)
+    N.require_device(images)
+    f = f.to(device=images.device, dtype=torch.float32)[:, :4].contiguous()
+    return N.f32c(images.detach()), f, code
+
+
+def _workspace(rows, H, W, device):
+    nbytes = N.load().sgdfr_fan_workspace_bytes(rows, H, W)
+    if nbytes < 0:
+        raise ValueError('landmarks: unsupported batch of %d images of %dx%d' % (rows, H, W))
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+
+
+def debug_views(debug, rows):
+    """The debug buffer as named views (csrc/fan.hip's DebugLayout): stem, conv4, hg (per stack), heatmaps (per stack)."""
+    out, o = {'hg': [], 'heatmaps': []}, 0
+
+    def take(shape):
+        nonlocal o
+        n = rows
+        for d in shape:
+            n *= d
+        v = debug[o:o + n].view(rows, *shape)
+        o += n
+        return v
+
+    out['stem'] = take((64, 128, 128))
+    out['conv4'] = take((256, MAP, MAP))
+    for _ in range(STACKS):
+        out['hg'].append(take((256, MAP, MAP)))
+        out['heatmaps'].append(take((POINTS, MAP, MAP)))
+    assert o == debug.numel(), (o, debug.numel())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- calls
+def crop(images, faces, input_range='255'):
+    """The front alone: the window of crop_torch around each face box with zero padding, resized to 256x256, / 255 -> [B,3,256,256]."""
+    x, f, code = _prepare(images, faces, input_range)
+    B, _, H, W = x.shape
+    if N.load().sgdfr_fan_workspace_bytes(B, H, W) < 0:
+        raise ValueError('landmarks: unsupported batch of %d images of %dx%d' % (B, H, W))
+    out = torch.empty((B, 3, CROP, CROP), dtype=torch.float32, device=x.device)
+    N.call('sgdfr_fan_crop_f32', N.ptr(x), N.ptr(f), B, H, W, code, N.ptr(out), N.stream())
+    return out
+
+
+def _check_crop(c):
+    if not torch.is_tensor(c) or c.dim() != 4 or tuple(c.shape[1:]) != (3, CROP, CROP) or c.shape[0] < 1:
+        raise ValueError('landmarks: expected [B,3,256,256] crops, got %s' % (tuple(c.shape) if torch.is_tensor(c) else type(c),))
+    N.require_device(c)
+
+
+def network(fan, crops, debug=False):
+    """The network alone: crops [B,3,256,256] in [0,1] -> the last stack's heatmaps [B,68,64,64]; with debug=True
+    (heatmaps, debug_views dict)."""
+    fan.check()
+    _check_crop(crops)
+    c = N.f32c(crops.detach())
+    B = c.shape[0]
+    lib = N.load()
+    ws, nbytes = _workspace(B, CROP, CROP, c.device)
+    hm = torch.empty((B, POINTS, MAP, MAP), dtype=torch.float32, device=c.device)
+    dbg = torch.empty(lib.sgdfr_fan_debug_elems(B), dtype=torch.float32, device=c.device) if debug else None
+    N.call('sgdfr_fan_network_f32', N.ptr(c), B, N.ptr(fan.packed()), N.ptr(hm), N.ptr(dbg), N.ptr(ws), nbytes, N.stream())
+    return (hm, debug_views(dbg, B)) if debug else hm
+
+
+def decode(heatmaps, faces):
+    """get_preds_fromhm for [B,68,64,64] heatmaps and their face boxes -> (pts_img [B,68,2], pts [B,68,2], boxes [B,4])."""
+    if not torch.is_tensor(heatmaps) or heatmaps.dim() != 4 or tuple(heatmaps.shape[1:]) != (POINTS, MAP, MAP) or heatmaps.shape[0] < 1:
+        raise ValueError('landmarks: expected [B,68,64,64] heatmaps, got %s' % (tuple(heatmaps.shape) if torch.is_tensor(heatmaps) else
+                                                                               type(heatmaps),))
+    f = _faces(faces, heatmaps)
+    N.require_device(heatmaps)
+    f = f.to(device=heatmaps.device, dtype=torch.float32)[:, :4].contiguous()
+    hm = N.f32c(heatmaps.detach())
+    B = hm.shape[0]
+    pts = torch.empty((B, POINTS, 2), dtype=torch.float32, device=hm.device)
+    pts_img = torch.empty_like(pts)
+    boxes = torch.empty((B, 4), dtype=torch.float32, device=hm.device)
+    N.call('sgdfr_fan_decode_f32', N.ptr(hm), N.ptr(f), B, N.ptr(pts), N.ptr(pts_img), N.ptr(boxes), N.stream())
+    return pts_img, pts, boxes
+
+
+def _forward(fan, images, faces, input_range, debug):
+    fan.check()
+    x, f, code = _prepare(images, faces, input_range)
+    B, _, H, W = x.shape
+    dev = x.device
+    lib = N.load()
+    ws, nbytes = _workspace(B, H, W, dev)
+    hm = torch.empty((B, POINTS, MAP, MAP), dtype=torch.float32, device=dev)
+    pts = torch.empty((B, POINTS, 2), dtype=torch.float32, device=dev)
+    pts_img = torch.empty_like(pts)
+    boxes = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    dbg = torch.empty(lib.sgdfr_fan_debug_elems(B), dtype=torch.float32, device=dev) if debug else None
+    N.call('sgdfr_fan_forward_f32', N.ptr(x), N.ptr(f), B, H, W, code, N.ptr(fan.packed()), N.ptr(hm), N.ptr(pts), N.ptr(pts_img),
+           N.ptr(boxes), N.ptr(dbg), N.ptr(ws), nbytes, N.stream())
+    return pts_img, pts, hm, boxes, dbg
+
+
+def get_landmarks(fan, images, faces, input_range='255'):
+    """LandmarksEstimation.get_landmarks for a whole batch in one pass.  images [B,3,H,W] float32 on the device, 0..255 values
+    (input_range='255', as the reference takes them) or GAN-range [-1,1] (input_range='gan': torch_range_1_to_255 is applied, the map
+    deca.encode applies, so one generated tensor feeds both); faces [B,4] (or [B,5], the score ignored) x0, y0, x1, y1 from the
+    caller's detector, a tensor or numbers.  Returns (pts_img [B,68,2] image pixels, integer-valued float32; pts [B,68,2] crop
+    pixels = preds * 4; heatmaps [B,68,64,64] of the last stack).  No host synchronisation; nothing is differentiable."""
+    pts_img, pts, hm, _, _ = _forward(fan, images, faces, input_range, False)
+    return pts_img, pts, hm
+
+
+def run_debug(fan, images, faces, input_range='255'):
+    """One pass with the debug switch on -> (pts_img, pts, heatmaps, boxes, debug_views dict).  For tests."""
+    pts_img, pts, hm, boxes, dbg = _forward(fan, images, faces, input_range, True)
+    return pts_img, pts, hm, boxes, debug_views(dbg, hm.shape[0])
+
+
+def kpt68_boxes(pts_img):
+    """detectors.FAN.run's box of the 68 points (detectors.py:38-41): [B,4] float32 left, top, right, bottom = min x, min y, max x,
+    max y, on the device, for deca.crop_matrix."""
+    if not torch.is_tensor(pts_img) or pts_img.dim() != 3 or tuple(pts_img.shape[1:]) != (POINTS, 2) or pts_img.shape[0] < 1:
+        raise ValueError('landmarks: expected [B,68,2] points, got %s' % (tuple(pts_img.shape) if torch.is_tensor(pts_img) else
+                                                                          type(pts_img),))
+    N.require_device(pts_img)
+    p = N.f32c(pts_img.detach())
+    boxes = torch.empty((p.shape[0], 4), dtype=torch.float32, device=p.device)
+    N.call('sgdfr_fan_boxes_f32', N.ptr(p), p.shape[0], N.ptr(boxes), N.stream())
+    return boxes

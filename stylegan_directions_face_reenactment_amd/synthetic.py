@@ -266,6 +266,47 @@ def synthetic_deca_encoder_state(seed):
     return out
 
 
+def synthetic_fan_state(seed):
+    """Seeded 2D-FAN-4 state dict in the 1129 keys of fan_model/models.py FAN(4) (landmarks.FAN) that keeps activations in range
+    through the ~100 residual blocks: conv filters behind a ReLU N(0, 2/fan_in), the 1x1 convs behind a sum (conv_last, l, al) and
+    bl N(0, 1/fan_in) with bl and al quartered, BatchNorm statistics near (0, 1); the scale of every ConvBlock's first BatchNorm around
+    0.2 -- each block then adds a few per cent to the variance its residual carries instead of doubling it -- and of bn_end around 0.3,
+    which takes back the growth of an hourglass (up1 + up2 at four levels).  Plain He initialisation puts the last heatmaps at 2e7.
+    95 MB: regenerated from the seed wherever it is needed, never stored."""
+    from collections import OrderedDict
+    from .landmarks import FAN
+    out = OrderedDict()
+    for key, t in FAN(4).state_dict().items():
+        shape = tuple(t.shape)
+        name = key.split('.')[0]
+        if key.endswith('num_batches_tracked'):
+            out[key] = torch.zeros(shape, dtype=torch.int64)
+        elif key.endswith('running_var'):
+            v = counter_normal(seed, key, int(np.prod(shape))) * 0.2 + 1.0
+            out[key] = torch.from_numpy(np.maximum(v, 0.3).astype(np.float32).reshape(shape))
+        elif key.endswith('running_mean'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.1)
+        elif len(shape) == 4:
+            fan_in = shape[1] * shape[2] * shape[3]
+            if name.startswith(('conv_last', 'l', 'bl', 'al')):
+                std = np.sqrt(1.0 / fan_in) * (0.25 if name.startswith(('bl', 'al')) else 1.0)
+            else:
+                std = np.sqrt(2.0 / fan_in)
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(std))
+        elif key.endswith('.bias'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.05)
+        elif key.endswith('.weight'):                             # BatchNorm scale
+            if key.endswith('.bn1.weight'):                       # a ConvBlock's first (the stem's key is 'bn1.weight')
+                out[key] = counter_tensor(seed, key, shape, 0.2, 0.02)
+            elif name.startswith('bn_end'):
+                out[key] = counter_tensor(seed, key, shape, 0.3, 0.03)
+            else:
+                out[key] = counter_tensor(seed, key, shape, 1.0, 0.1)
+        else:
+            raise KeyError(key)
+    return out
+
+
 def _counter_index(seed, key, shape, n):
     """Integers in 0..n-1 from the counter generator."""
     count = int(np.prod(shape))
