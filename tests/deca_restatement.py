@@ -191,6 +191,55 @@ def warp_affine_composed(src, theta, dsize=(CROP, CROP), align_corners=False):
     return F.grid_sample(src, grid, mode='bilinear', padding_mode='zeros', align_corners=align_corners)
 
 
+# ---------------------------------------------------------------------------------------------------------------- front geometries
+# Crops the 'kpt68' boxes of a 256^2 picture never ask for (test_gpu_deca_fan_plans): name -> (H, W, ('box', [l, t, r, b]) through
+# deca.crop_matrix, or ('matrix', 2x3) as it is).  'singular' is singular on paper only: in float32 the two products 0.07 * 0.05 are
+# equal when each is rounded, but the library is built with -ffp-contract=on, the kernel's m0 m4 - m1 m3 becomes
+# fma(m0, m4, -(m1 m3)) and gives the product's rounding error, about +-4e-11 -- above the kernel's 1e-12 switch, so this case takes
+# the inverse branch with an inverse of ~1e9 and a candidate box that the clamps open to the whole crop.  'singular_exact' has
+# entries that are powers of two: both products are exact, the determinant is 0 in either form, and the adjoint's all-candidates
+# fallback runs.  'near_singular' has det ~ 1e-5 with an inverse of ~1e4.  The three stay at 32^2: they visit 224^2 candidates per
+# source pixel.
+FRONT_GEOMETRIES = {
+    'down_4.6': (1024, 1024, ('box', [130.0, 150.0, 890.0, 900.0])),
+    'up_8': (64, 48, ('box', [14.0, 20.0, 34.0, 41.0])),
+    'rotation_shear': (256, 256, ('matrix', [[0.7794, -0.45, 40.0], [0.45, 1.1258, -30.0]])),
+    'mirrored': (200, 300, ('matrix', [[-1.1, 0.0, 280.0], [0.0, 0.8, 10.0]])),
+    'singular': (32, 32, ('matrix', [[0.07, 0.07, 1.0], [0.05, 0.05, 3.0]])),
+    'singular_exact': (32, 32, ('matrix', [[0.0625, 0.0625, 1.0], [0.03125, 0.03125, 3.0]])),
+    'near_singular': (32, 32, ('matrix', [[0.1, 0.1, 1.0], [0.1, 0.1001, 2.0]])),
+}
+NON_SINGULAR = ('down_4.6', 'up_8', 'rotation_shear', 'mirrored')
+
+
+def front_matrix(name, crop_matrix):
+    """The float32 [1,2,3] matrix of a FRONT_GEOMETRIES case; `crop_matrix` is deca.crop_matrix (host arithmetic in fp64)."""
+    H, W, (kind, v) = FRONT_GEOMETRIES[name]
+    if kind == 'box':
+        return crop_matrix(torch.tensor([v], dtype=torch.float64), (H, W))
+    return torch.tensor([v], dtype=torch.float32)
+
+
+def resized_matrix(M, src_hw, dst_hw):
+    """The matrix that samples an image resized from src_hw to dst_hw where M sampled the original (pixel centres scaled about 0)."""
+    sy, sx = dst_hw[0] / src_hw[0], dst_hw[1] / src_hw[1]
+    return (M.double() * torch.tensor([[sx], [sy]], dtype=torch.float64)).float()
+
+
+# pose[:3] rows for the angle branches: zero pose (t2 = 0), a regular row, R20 = +1 and -1 (the two |R20| > 0.998 branches: a
+# rotation by -+pi/2 about y has R20 = -sin(theta)), and a row with R20 = 0.9969, just inside the regular branch
+ANGLE_ROWS = [[0.0, 0.0, 0.0], [0.3, -0.2, 0.1], [0.0, -math.pi / 2, 0.0], [0.0, math.pi / 2, 0.0], [0.02, -1.4925, 0.01]]
+
+
+def r20(pose3):
+    """R20 of batch_axis2euler's rotation matrix for pose3 [B,3] (the quantity the angle branches switch on)."""
+    t = pose3.norm(dim=1).clamp_min(1e-300)
+    w = torch.cos(0.5 * t)
+    k = torch.sin(0.5 * t) / t
+    x, y, z = (pose3 * k.unsqueeze(1)).unbind(1)
+    return 2 * x * z - 2 * w * y
+
+
 # ---------------------------------------------------------------------------------------------------------------- kat12 inputs
 # name -> (image shape, 'kpt68' boxes): B=1 at 256^2 with a box partly outside the image; B=2 at 200x300 (H x W), row 1 with values
 # beyond +-1

@@ -20,15 +20,40 @@ CASES = {
 }
 
 
-def fixture_inputs(S, seed, name):
-    """(images [B,3,H,W] float32 with 0..255 values, faces [B,4] float32), regenerated from counter keys."""
-    B, H, W, faces = CASES[name]
-    x = S.counter_tensor(seed, 'fan.case.%s.images' % name, (B, 3, H, W), 127.5, 60.0).clamp(0, 255)
-    # a smooth component, so that the crop is not white noise at every scale
+# geometries of the front beyond the fixture's (test_gpu_deca_fan_plans): name -> (rows, H, W, face boxes).  The integer windows
+# (GEO_WINDOWS, what `windows` gives for them in float32): 'inside1024' lies wholly inside a large image (pure down-scaling by 3.5),
+# 'small96' leaves a small image on every side, 'tiny_up' is 67 pixels wide (up-scaled by 3.8), 'wide' hangs half out of a 120 x 640
+# strip, 'outside' misses the image (a zero crop: the heatmaps come from the biases alone), 'huge' holds the image as a speck.
+GEO_CASES = {
+    'inside1024': (1, 1024, 1024, [[300.0, 280.0, 700.0, 760.0]]),
+    'small96': (2, 96, 80, [[20.0, 18.0, 61.0, 70.0], [-4.0, 30.0, 40.0, 90.0]]),
+    'tiny_up': (1, 256, 256, [[100.0, 100.0, 130.0, 136.0]]),
+    'wide': (1, 120, 640, [[200.0, 5.0, 330.0, 118.0]]),
+    'outside': (1, 256, 256, [[900.0, 900.0, 1100.0, 1120.0]]),
+    'huge': (1, 64, 64, [[-400.0, -380.0, 470.0, 520.0]]),
+}
+
+
+def images(S, seed, key, B, H, W):
+    """Seeded [B,3,H,W] float32 images with 0..255 values under the counter key `key`: noise plus a smooth component, so that the
+    crop is not white noise at every scale."""
+    x = S.counter_tensor(seed, key, (B, 3, H, W), 127.5, 60.0).clamp(0, 255)
     yy = torch.linspace(0, 1, H).view(1, 1, H, 1)
     xx = torch.linspace(0, 1, W).view(1, 1, 1, W)
     x = (0.5 * x + 127.5 * (0.5 + 0.5 * torch.sin(6.0 * xx + 2.0 * yy) * torch.cos(5.0 * yy))).clamp(0, 255)
-    return x.contiguous(), torch.tensor(faces, dtype=torch.float32)
+    return x.contiguous()
+
+
+def fixture_inputs(S, seed, name):
+    """(images [B,3,H,W] float32 with 0..255 values, faces [B,4] float32), regenerated from counter keys."""
+    B, H, W, faces = CASES[name]
+    return images(S, seed, 'fan.case.%s.images' % name, B, H, W), torch.tensor(faces, dtype=torch.float32)
+
+
+def geo_inputs(S, seed, name):
+    """The same for a GEO_CASES geometry, under the key 'fan.geo.<name>.images'."""
+    B, H, W, faces = GEO_CASES[name]
+    return images(S, seed, 'fan.geo.%s.images' % name, B, H, W), torch.tensor(faces, dtype=torch.float32)
 
 
 def to_255(x):
@@ -251,6 +276,22 @@ def decode(hm, faces):
     pts_img = pre.trunc().to(torch.float32)
     boxes = torch.cat([pts_img.min(1).values, pts_img.max(1).values], 1)
     return {'idx': idx, 'pts': preds * 4, 'pts_img': pts_img, 'pre': pre, 'boxes': boxes, 'interior': interior, 'dx': dx, 'dy': dy}
+
+
+def safe_landmarks(hm64, faces, margin):
+    """[B,68] bool: the landmarks whose decode cannot depend on a heatmap deviation below margin / 16 -- the rule the fixture's script
+    (scripts/make_golden_fan.py) asserts for every landmark of kat13, per landmark: in fp64 the top-2 margin is >= `margin`, both
+    neighbour differences of an interior maximum are >= `margin`, and both image coordinates are >= 1e-3 from an integer before
+    the truncation (centre and scale in fp64)."""
+    B = hm64.shape[0]
+    d = decode(hm64, faces)
+    top2 = hm64.reshape(B, POINTS, -1).topk(2, dim=2).values
+    safe = (top2[..., 0] - top2[..., 1]) >= margin
+    safe &= ~d['interior'] | (torch.minimum(d['dx'].abs(), d['dy'].abs()) >= margin)
+    c64, s64 = centre_scale(faces.double())
+    pre64 = torch.stack([inv_transform_float((d['pts'][b] / 4).double(), c64[b], s64[b], 64.0) for b in range(B)])
+    safe &= ((pre64 - pre64.round()).abs() >= 1e-3).all(2)
+    return safe
 
 
 def handmade_heatmaps():

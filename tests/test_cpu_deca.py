@@ -228,3 +228,18 @@ def test_native_symbols_and_sizes():
     arr = (ctypes.c_void_p * _native.DECA_PARAMS)()
     rc = lib.sgdfr_deca_prepack_f32(arr, ctypes.c_void_p(8), None)
     assert rc != 0 and b'parameter 0 is null' in lib.sgdfr_last_error()
+
+
+def test_plan_rule_reproduces_the_documented_split_counts():
+    """The split-K rule as test_gpu_deca_fan_plans restates it (the GPU tests assert the counted finish launches against it) gives
+    DESIGN 4.15's counts -- 45 / 44 convs split K at B = 1, 43 / 41 at 3, 18 / 17 at 16 and 17, 2 / 1 at 48 (of 55 / 50) -- and
+    4.16's: 188, 165, 132, 108, 96 of 191."""
+    import test_gpu_deca_fan_plans as P
+    fwd, bwd = P.deca_layers()
+    assert (len(fwd), len(bwd), len(P.fan_layers())) == (55, 50, 191)
+    deca = [(P.planned_finishes(fwd, B), P.planned_finishes(bwd, B)) for B in P.ROW_COUNTS]
+    fan = [P.planned_finishes(P.fan_layers(), B) for B in P.ROW_COUNTS]
+    print('plan rule: deca finishes forward / backward %s; fan %s' % (deca, fan))
+    assert P.ROW_COUNTS == (1, 3, 16, 17, 48)
+    assert deca == [(45, 44), (43, 41), (18, 17), (18, 17), (2, 1)]
+    assert fan == [188, 165, 132, 108, 96]
