@@ -115,7 +115,13 @@ __global__ __launch_bounds__(256) void pixelnorm_kernel(const float* __restrict_
     for (int j = lane; j < D; j += 64) y[(int64_t)row * D + j] = xr[j] * r;
 }
 
-// adjoint of pixelnorm: y = x*r, r = rsqrt(mean x^2 + eps)  =>  dx = r*g - x * r^3 * mean(g*x); one wave per row
+// adjoint of pixelnorm: y = x*r, r = rsqrt(mean x^2 + eps)  =>  dx = r*g - x * r^3 * mean(g*x); one wave per row.
+// Evaluated as  dx_j = r^3 * (eps*g_j + (g_j * sum x^2 - x_j * sum g*x) / D)  with the two row sums and the combination in fp64:
+// the component of g along x is scaled by eps*r^2 only, so r*g and x*r^3*mean(g*x) cancel to 1e-8 of their size there (for D = 1
+// always), which the fp32 difference of the two products cannot resolve; in this form the eps term stands alone.
+// The fp64 sums, shuffles and sqrt are there for that degenerate case (D = 1, nearly parallel g and x); the callers run D = 512 on
+// a handful of rows, where the kernel is launch-bound.  Its cost has been measured through the end-to-end benchmark only (unchanged),
+// not for the kernel alone.
 __global__ __launch_bounds__(256) void pixelnorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                            float* __restrict__ dx, int B, int D, float eps) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -123,18 +129,22 @@ __global__ __launch_bounds__(256) void pixelnorm_bwd_kernel(const float* __restr
     if (row >= B) return;
     const float* xr = x + (int64_t)row * D;
     const float* gr = g + (int64_t)row * D;
-    float sq = 0.f, gx = 0.f;
+    double sq = 0.0, gx = 0.0;
     for (int j = lane; j < D; j += 64) {
-        sq = fmaf(xr[j], xr[j], sq);
-        gx = fmaf(gr[j], xr[j], gx);
+        const double xv = xr[j];
+        sq = fma(xv, xv, sq);
+        gx = fma((double)gr[j], xv, gx);
     }
     for (int o = 32; o > 0; o >>= 1) {
         sq += __shfl_xor(sq, o, 64);
         gx += __shfl_xor(gx, o, 64);
     }
-    const float r = rsqrtf(sq / (float)D + eps);
-    const float c = r * r * r * (gx / (float)D);
-    for (int j = lane; j < D; j += 64) dx[(int64_t)row * D + j] = r * gr[j] - xr[j] * c;
+    const double r = 1.0 / sqrt(sq / (double)D + (double)eps);
+    const double r3 = r * r * r, inv_d = 1.0 / (double)D;
+    for (int j = lane; j < D; j += 64) {
+        const double gv = gr[j], xv = xr[j];
+        dx[(int64_t)row * D + j] = (float)(r3 * ((double)eps * gv + (gv * sq - xv * gx) * inv_d));
+    }
 }
 
 // ---------------------------------------------------------------- latent prepare

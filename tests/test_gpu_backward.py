@@ -3,6 +3,7 @@ vs the dL/dA golden captured from the real reference through generate_image (KAT
 import pytest
 import torch
 
+from dense_refs import demod_dq_reference, style_bwd_reference
 from util import O, S, SEED, golden, hip_generator, maxabs, synthetic_state, t
 
 @pytest.fixture(autouse=True, params=['fp16x3', 'fp32'])
@@ -349,27 +350,17 @@ def test_batched_style_backward_and_small_parameter_gradients_match_torch():
                 e['a'], e['d'], e['s'], e['qt'] = sums[:, :, 2], rnd(B, cout).abs() + 0.5, rnd(B, cin), rnd(cin, cout).abs()
         layers.append((kind, e))
     glat = F_.styles_batched_bwd([e for _, e in layers], B, L, D, latent=latent)
-    want = torch.zeros(B, L, D, dtype=torch.float64, device=dev)
-    for kind, e in layers:
-        cin = e['mod_w'].shape[0]
-        if kind == 'rgb':
-            ds = (e['rgb_r'].double() * e['rgb_w'].double().unsqueeze(0)).sum(1) / cin ** 0.5
-        elif kind == 'plain':
-            ds = e['gs'].double()
-        else:
-            a, d = e['a'].double(), e['d'].double()
-            ds = e['gs'].double() + e['s'].double() * ((-(a / d) * d ** 3) @ e['qt'].double().t())
-        want[:, e['latent_index']] += ds @ e['mod_w'].double() / D ** 0.5
-        assert _rel(e['gmod_w'], ds.t() @ latent[:, e['latent_index']].double() / D ** 0.5) <= 2e-5
-        assert _rel(e['gmod_b'], ds.sum(0)) <= 2e-5
+    want, per = style_bwd_reference(layers, latent, B, L, D)          # (the fp64 expressions: tests/dense_refs.py)
+    for (kind, e), (ds, gmod_w, gmod_b) in zip(layers, per):
+        assert _rel(e['gmod_w'], gmod_w) <= 2e-5
+        assert _rel(e['gmod_b'], gmod_b) <= 2e-5
     assert _rel(glat, want) <= 2e-5
     # dL/dQ of the demodulation
     cout, cin = 48, 64
     sums, d, s_ = rnd(B, cout, 3), rnd(B, cout).abs() + 0.5, rnd(B, cin)
     a = sums[:, :, 2]
     dq = F_.demod_dq(a, d, s_)
-    coeff = (a.double() / d.double()) * d.double() ** 3 * -0.5
-    assert _rel(dq, coeff.t() @ (s_.double() ** 2)) <= 2e-5
+    assert _rel(dq, demod_dq_reference(a, d, s_)) <= 2e-5
     # bias / noise strength / ToRGB weight / ToRGB bias gradients in one launch
     C, HW = 40, 33 * 33
     sums2, r_rgb, s_rgb, g_rgb = rnd(B, C, 3), rnd(B, 3, C), rnd(B, C), rnd(B, 3, 33, 33)
