@@ -717,6 +717,47 @@ int sgdfr_fan_forward_f32(const float* x, const float* faces, int rows, int H, i
                           float* heatmaps, float* pts, float* pts_img, float* boxes, float* debug, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* The S3FD face detector in eval mode (libs/face_models/sfd/net_s3fd.py s3fd, detect.py:36-81 batch_detect, bbox.py:44-66 nms and
+ * :93-111 decode, sfd_detector.py:31-47 detect_from_batch), csrc/s3fd.hip.  Forward only.
+ * Images x [rows,3,H,W] fp32 with 0..255 values, 1..256 rows, each side 32..4096, rows*H*W <= 2^24.  subtract_mean != 0 subtracts
+ * (104, 117, 123) per channel inside the image as detect() does; batch_detect, the path the reference uses, does not.
+ * sgdfr_s3fd_prepack_f32: params = host array of 50 device pointers: w [Cout,Cin,k,k] and b [Cout] of the 19 trunk convs in forward
+ *   order (conv1_1 ... conv5_3, fc6, fc7, conv6_1, conv6_2, conv7_1, conv7_2), then per level (conv3_3, conv4_3, conv5_3, fc7,
+ *   conv6_2, conv7_2) the conf and loc filters concatenated, w [conf+4,C,3,3] and b [conf+4] (conf = 4 at level 0, else 2), the
+ *   L2Norm weight of levels 0-2 folded in per input channel on the host -> pack of sgdfr_s3fd_pack_elems() floats (rebuild it
+ *   whenever a parameter changes).
+ * sgdfr_s3fd_level_dims: hw[12] = (h, w) of the six level maps for an H x W image.
+ * sgdfr_s3fd_network_f32: maps receives sgdfr_s3fd_map_elems(rows, H, W) floats: per level cls [rows,2,h,w] (level 0 after the
+ *   max-out of its three background logits) then reg [rows,4,h,w], the twelve outputs of s3fd.forward in its order.  debug (NULL:
+ *   off) receives sgdfr_s3fd_debug_elems(rows, H, W) floats: conv1_2, conv2_2, conv3_3, conv4_3, conv5_3, fc6, fc7, conv6_2, conv7_2
+ *   behind their ReLU and in front of a pool, each [rows,C,h,w], then the reciprocal L2 norms of conv3_3, conv4_3, conv5_3 [rows,h,w].
+ * sgdfr_s3fd_candidates_f32: heads = host array of six device pointers, level l [rows, conf+4, h_l, w_l] (the raw head output, conf
+ *   channels first), hw = host array of the twelve map sizes.  Max-out, softmax score of channel 1, score > threshold, box decode
+ *   against the prior (stride 2^(l+2), centre stride/2 + index*stride, size 4 strides, variances 0.1 / 0.2) -> cand
+ *   [rows,capacity,5] = x1, y1, x2, y2, score in (level, y, x) order, count [rows] = the true number even beyond capacity, valid
+ *   [rows] = 0 where count > capacity (the list then holds the first `capacity`).  capacity 1..16384.
+ * sgdfr_s3fd_nms_f32: per row the first min(count, capacity) candidates: those above 0.5 sorted by score descending (ties: candidate
+ *   index ascending), greedy suppression at IoU > 0.3 with "+ 1" areas in float32 -> boxes [rows,capacity,5] in descending score
+ *   order (zeros behind the kept ones), index [rows,capacity] = each kept box's candidate index (-1 behind), kept [rows].
+ * sgdfr_s3fd_forward_f32: network + candidates + nms in one call; boxes, index and kept may all be NULL (no selection), maps and
+ *   debug may be NULL.
+ * workspace: device scratch of at least sgdfr_s3fd_workspace_bytes(rows, H, W) bytes.  The split-K plan follows rows, H and W only.
+ * Deterministic (no float atomics), no host synchronisation, everything on `stream`: counts stay on the device. */
+int64_t sgdfr_s3fd_pack_elems(void);
+int64_t sgdfr_s3fd_debug_elems(int rows, int H, int W);
+int64_t sgdfr_s3fd_map_elems(int rows, int H, int W);
+int64_t sgdfr_s3fd_workspace_bytes(int rows, int H, int W);
+int sgdfr_s3fd_level_dims(int H, int W, int* hw);
+int sgdfr_s3fd_prepack_f32(const float* const* params, float* pack, void* stream);
+int sgdfr_s3fd_network_f32(const float* x, int rows, int H, int W, int subtract_mean, const float* pack, float* maps, float* debug,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_s3fd_candidates_f32(const float* const* heads, const int* hw, int rows, float threshold, int capacity, float* cand, int* count,
+                              int* valid, void* stream);
+int sgdfr_s3fd_nms_f32(const float* cand, const int* count, int rows, int capacity, float* boxes, int* index, int* kept, void* stream);
+int sgdfr_s3fd_forward_f32(const float* x, int rows, int H, int W, int subtract_mean, const float* pack, float threshold, int capacity,
+                           float* cand, int* count, int* valid, float* boxes, int* index, int* kept, float* maps, float* debug,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

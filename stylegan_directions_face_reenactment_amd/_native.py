@@ -194,6 +194,16 @@ SIGNATURES['sgdfr_fan_forward_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _i, _c_f32p
                                        ctypes.c_void_p, _i64, ctypes.c_void_p]
 FAN_PARAMS = 735        # pointers sgdfr_fan_prepack_f32 takes
 FAN_RANGE_255, FAN_RANGE_GAN = 0, 1      # include/sgdfr.h SGDFR_FAN_RANGE_*
+_ip = ctypes.c_void_p                    # int* on the device
+SIGNATURES['sgdfr_s3fd_level_dims'] = [_i, _i, ctypes.POINTER(ctypes.c_int)]
+SIGNATURES['sgdfr_s3fd_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_s3fd_network_f32'] = [_c_f32p, _i, _i, _i, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+SIGNATURES['sgdfr_s3fd_candidates_f32'] = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), _i, _f, _i, _c_f32p, _ip, _ip,
+                                           ctypes.c_void_p]
+SIGNATURES['sgdfr_s3fd_nms_f32'] = [_c_f32p, _ip, _i, _i, _c_f32p, _ip, _ip, ctypes.c_void_p]
+SIGNATURES['sgdfr_s3fd_forward_f32'] = [_c_f32p, _i, _i, _i, _i, _c_f32p, _f, _i, _c_f32p, _ip, _ip, _c_f32p, _ip, _ip, _c_f32p, _c_f32p,
+                                        ctypes.c_void_p, _i64, ctypes.c_void_p]
+S3FD_PARAMS = 50        # pointers sgdfr_s3fd_prepack_f32 takes
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
 OPTIONAL_SIGNATURES = {'sgdfr_mfma_ceiling_probe': [_i, _i, _i, _i, _i, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]}
@@ -252,6 +262,11 @@ def load():
     lib.sgdfr_fan_debug_elems.restype = ctypes.c_int64
     lib.sgdfr_fan_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.sgdfr_fan_workspace_bytes.restype = ctypes.c_int64
+    lib.sgdfr_s3fd_pack_elems.argtypes = []
+    lib.sgdfr_s3fd_pack_elems.restype = ctypes.c_int64
+    for name in ('sgdfr_s3fd_debug_elems', 'sgdfr_s3fd_map_elems', 'sgdfr_s3fd_workspace_bytes'):
+        getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        getattr(lib, name).restype = ctypes.c_int64
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():

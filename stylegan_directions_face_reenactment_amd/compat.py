@@ -8,9 +8,10 @@ Only the modules of the hot path are aliased; everything else u
 resolving to the reference checkout on sys.path.  ``install_lpips(state_dict)`` (opt-in) additionally mounts the HIP LPIPS at
 ``libs.criteria.lpips.lpips`` so that unchanged ``LPIPS(net_type='alex')`` calls get it with those weights (no torchvision, no
 download); ``install_id_loss(path)`` (opt-in) mounts the HIP identity loss at ``libs.criteria.id_loss`` the same way.
-There is no ``install_landmarks``: ``LandmarksEstimation`` (libs/face_models/landmarks_estimation.py) owns the S3FD face detector as
-well as the FAN network, and mounting half a class helps nobody; call ``landmarks.get_landmarks`` with the detector's boxes instead
-(INTEGRATION.md).  ``libs.utilities.generic`` is NOT replaced wholesale
+``install_face_detector(state_dict)`` (opt-in) mounts the HIP S3FD detector at ``libs.face_models.sfd.sfd_detector`` so that an
+unchanged ``SFDDetector(device, path)`` (landmarks_estimation.py:118) gets it.  There is no ``install_landmarks``:
+``LandmarksEstimation`` crops and runs one face at a time around the FAN network; call ``face_detector.detect_landmarks`` or
+``landmarks.get_landmarks`` instead.  ``libs.utilities.generic`` is NOT replaced wholesale
 (it also holds DECA glue); call ``patch_generic(module)`` to swap in the two fused functions.
 """
 import importlib
@@ -112,3 +113,43 @@ def install_id_loss(pretrained_model_path=None):
     mod.__doc__ = 'HIP identity loss mounted by stylegan_directions_face_reenactment_amd.compat.install_id_loss'
     _mount(ID_LOSS_ALIAS, mod)
     return ID_LOSS_ALIAS
+
+
+FACE_DETECTOR_ALIAS = 'libs.face_models.sfd.sfd_detector'
+
+
+def install_face_detector(state_dict=None):
+    """Mount a module at libs.face_models.sfd.sfd_detector whose SFDDetector(device, path_to_detector) is the HIP S3FD detector:
+    an unchanged `SFDDetector(device, path)` loads `path` with torch.load as sfd_detector.py:24 does (or takes `state_dict` when one is
+    given here and no path), moves the network to the GPU and answers detect_from_batch(tensor) with the reference's lists (which
+    synchronises, as the reference does).  reference_scale / reference_x_shift / reference_y_shift are the reference's 195 / 0 / 0.
+    Parent packages that cannot be imported are created empty."""
+    import torch
+    from . import face_detector as hip_fd
+    sd0 = None if state_dict is None else dict(state_dict)
+    if sd0 is not None:
+        hip_fd.S3FD().load_state_dict(sd0)           # fail here, not at the first SFDDetector() of the caller
+    _parent_packages(FACE_DETECTOR_ALIAS)
+
+    class SFDDetector(object):
+        def __init__(self, device, path_to_detector=None, verbose=False):
+            self.device, self.verbose = device, verbose
+            if path_to_detector is None and sd0 is None:
+                raise ValueError('SFDDetector: no path_to_detector and no state dict given to install_face_detector')
+            self.face_detector = hip_fd.S3FD()
+            self.face_detector.load_state_dict(torch.load(path_to_detector) if path_to_detector is not None else sd0)
+            self.face_detector.to('cuda')
+
+        def detect_from_batch(self, tensor):
+            return hip_fd.detect_from_batch(self.face_detector, tensor.float())
+
+        reference_scale = property(lambda self: 195)
+        reference_x_shift = property(lambda self: 0)
+        reference_y_shift = property(lambda self: 0)
+
+    mod = types.ModuleType(FACE_DETECTOR_ALIAS)
+    mod.SFDDetector = SFDDetector
+    mod.s3fd = hip_fd.S3FD
+    mod.__doc__ = 'HIP S3FD face detector mounted by stylegan_directions_face_reenactment_amd.compat.install_face_detector'
+    _mount(FACE_DETECTOR_ALIAS, mod)
+    return FACE_DETECTOR_ALIAS

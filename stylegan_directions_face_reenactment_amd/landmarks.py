@@ -19,8 +19,8 @@ The crop: `transforms.Resize` on a tensor is F.interpolate(mode='bilinear', alig
 torchvision the reference was written for.  torchvision was not available when this was written, so the resize is pinned only
 against F.interpolate composed that way: the composition itself is UNVERIFIED against torchvision.
 
-The S3FD face detector stays with the caller: face boxes come in as numbers.  The 3D landmark type (ResNetDepth) and flip_input are
-not built.
+Face boxes come in as numbers or as a device tensor; face_detector.py (S3FD on csrc/s3fd.hip) produces them and
+face_detector.detect_landmarks chains the two.  The 3D landmark type (ResNetDepth) and flip_input are not built.
 """
 import ctypes
 from collections import OrderedDict

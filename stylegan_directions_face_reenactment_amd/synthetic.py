@@ -307,6 +307,48 @@ def synthetic_fan_state(seed):
     return out
 
 
+# synthetic_s3fd_state: per level (conf filter gain, loc filter gain, face-logit bias); gains multiply N(0, 1/fan_in).  The figures
+# are tuned at seed 20261018 (scripts/make_golden_s3fd.py): behind the L2Norm most of a logit is a constant over the map (the taps
+# are positive), so the conf gains of levels 0-2 are large to give the part that varies a spread of 4-5, and the biases centre it.
+S3FD_EXTRA_GAIN = {'fc6': 0.02}                       # the trunk hands fc6 values of O(100): fc6 brings them to O(1) for levels 3-5
+S3FD_HEADS = {'conv3_3_norm': (16.0, 0.9, -7.5), 'conv4_3_norm': (32.0, 0.9, -1.5), 'conv5_3_norm': (13.0, 0.9, -5.5),
+              'fc7': (2.0, 0.45, -6.0), 'conv6_2': (3.0, 0.45, -5.4), 'conv7_2': (3.0, 0.45, -1.0)}
+
+
+def synthetic_s3fd_state(seed):
+    """Seeded S3FD state dict in the 65 keys of sfd/net_s3fd.py s3fd (face_detector.S3FD) whose detections are usable as a fixture.
+    Trunk filters are He-scaled N(0, 2/fan_in) with small biases; a plain He state throughout saturates levels 4-5 at score 1.0 and
+    puts |loc| of levels 3-5 at 50-350 (exp(0.2 loc) overflows), because only levels 0-2 are normalised.  So fc6 is scaled down to
+    hand O(1) values to the un-normalised levels, the L2Norm weights stay at their constructor scales (10 / 8 / 5) with a few per
+    cent of jitter, loc filters are scaled for |loc| of O(1), and conf filters are scaled up with a negative face-logit bias per
+    level: the score distribution gets a heavy tail, so that most positions fall below 0.05, a few lie between 0.05 and 0.5 and a
+    few above 0.5 on every level.  90 MB: regenerated from the seed wherever it is needed, never stored."""
+    from collections import OrderedDict
+    from .face_detector import S3FD
+    out = OrderedDict()
+    for key, t in S3FD().state_dict().items():
+        shape = tuple(t.shape)
+        name = key.rsplit('.', 1)[0]
+        head = name.rsplit('_mbox_', 1)[0] if '_mbox_' in name else None
+        if len(shape) == 4 and head is None:
+            fan_in = shape[1] * shape[2] * shape[3]
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(2.0 / fan_in) * S3FD_EXTRA_GAIN.get(name, 1.0)))
+        elif len(shape) == 4:
+            conf_gain, loc_gain, _ = S3FD_HEADS[head]
+            fan_in = shape[1] * shape[2] * shape[3]
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(1.0 / fan_in) * (conf_gain if name.endswith('conf') else loc_gain)))
+        elif name.endswith('_norm'):
+            scale = {'conv3_3_norm': 10.0, 'conv4_3_norm': 8.0, 'conv5_3_norm': 5.0}[name]
+            out[key] = counter_tensor(seed, key, shape, scale, 0.03 * scale)
+        elif head is not None and name.endswith('conf'):
+            b = counter_tensor(seed, key, shape, 0.0, 0.05)
+            b[-1] += S3FD_HEADS[head][2]
+            out[key] = b
+        else:
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.05)
+    return out
+
+
 def _counter_index(seed, key, shape, n):
     """Integers in 0..n-1 from the counter generator."""
     count = int(np.prod(shape))
