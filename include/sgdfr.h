@@ -758,6 +758,36 @@ int sgdfr_s3fd_forward_f32(const float* x, int rows, int H, int W, int subtract_
                            float* cand, int* count, int* valid, float* boxes, int* index, int* kept, float* maps, float* debug,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The e4e W+ encoder in eval mode (libs/gan/encoder4editing/psp_encoders.py:33-53 and :122-199 Encoder4Editing(50, 'ir_se', R),
+ * helpers.py:57-140), csrc/e4e.hip.  Forward only, as in the reference (every call there is under no_grad).
+ * Images x [rows,3,R,R] fp32 in [-1,1]; R a multiple of 16 in 32..256 (so that every style head ends at 1x1), 1..256 rows,
+ * rows*R*R <= 2^24.  w receives [rows, style_count, 512] with style_count = sgdfr_e4e_style_count(R) = 2 floor(log2 R) - 2:
+ * w[:,0] = w0, w[:,i] = w0 + delta_i.  No latent average is added, as in the reference.
+ * sgdfr_e4e_prepack_f32: params = host array of sgdfr_e4e_param_count(R) device pointers (423 at R = 256), BatchNorms folded on the
+ *   host to (g, h) = (w rsqrt(var + eps), b - mean g):
+ *     stem: w0 [64,3,3,3] with the stem BN folded in, b0 [64], PReLU slope a0 [64];
+ *     per unit (24, as for the identity loss): BN1 g1 [Cin], h1 [Cin], conv1 w1 [D,Cin,3,3], PReLU slope a1 [D], conv2 w2 [D,D,3,3]
+ *       with BN2 folded in, b2 [D], SE fc1 [D/16,D], fc2 [D,D/16], the shortcut conv wsc [D,Cin] with its BN folded in and bsc [D]
+ *       (both NULL where Cin == D: the shortcut is a strided subsample);
+ *     latlayer1 w [512,256], b [512]; latlayer2 w [512,128], b [512];
+ *     per style head, in order: per conv (4 for heads 0-2, 5 for heads 3-6, 6 behind) w [512,512,3,3], b [512]; then the EqualLinear
+ *       weight times 1/sqrt(512) [512,512] and its bias [512]
+ *   -> pack of sgdfr_e4e_pack_elems(R) floats (rebuild it whenever a parameter changes).
+ * sgdfr_e4e_forward_f32: debug (NULL: off) receives sgdfr_e4e_debug_elems(rows, R) floats: the stem [rows,64,R,R], unit 0's output
+ *   [rows,64,R/2,R/2], unit 3's [rows,128,R/4,R/4], c1 [rows,128,R/4,R/4], c2 [rows,256,R/8,R/8], c3 [rows,512,R/16,R/16],
+ *   p2 [rows,512,R/8,R/8], p1 [rows,512,R/4,R/4] and the head vectors in front of the EqualLinears [rows,style_count,512].
+ * A bad R, rows < 1 or a workspace below sgdfr_e4e_workspace_bytes(rows, R) bytes is an error (the size functions return -1 for
+ *   sizes out of range).  The split-K plan follows rows and R only.
+ * Deterministic (no float atomics), no host synchronisation, everything on `stream`. */
+int sgdfr_e4e_style_count(int R);
+int sgdfr_e4e_param_count(int R);
+int64_t sgdfr_e4e_pack_elems(int R);
+int64_t sgdfr_e4e_debug_elems(int rows, int R);
+int64_t sgdfr_e4e_workspace_bytes(int rows, int R);
+int sgdfr_e4e_prepack_f32(const float* const* params, int R, float* pack, void* stream);
+int sgdfr_e4e_forward_f32(const float* x, int rows, int R, const float* pack, float* w, float* debug, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

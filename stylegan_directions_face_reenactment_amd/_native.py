@@ -204,6 +204,9 @@ SIGNATURES['sgdfr_s3fd_nms_f32'] = [_c_f32p, _ip, _i, _i, _c_f32p, _ip, _ip, cty
 SIGNATURES['sgdfr_s3fd_forward_f32'] = [_c_f32p, _i, _i, _i, _i, _c_f32p, _f, _i, _c_f32p, _ip, _ip, _c_f32p, _ip, _ip, _c_f32p, _c_f32p,
                                         ctypes.c_void_p, _i64, ctypes.c_void_p]
 S3FD_PARAMS = 50        # pointers sgdfr_s3fd_prepack_f32 takes
+SIGNATURES['sgdfr_e4e_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_e4e_forward_f32'] = [_c_f32p, _i, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+E4E_PARAMS_256 = 423    # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
 OPTIONAL_SIGNATURES = {'sgdfr_mfma_ceiling_probe': [_i, _i, _i, _i, _i, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]}
@@ -266,6 +269,14 @@ def load():
     lib.sgdfr_s3fd_pack_elems.restype = ctypes.c_int64
     for name in ('sgdfr_s3fd_debug_elems', 'sgdfr_s3fd_map_elems', 'sgdfr_s3fd_workspace_bytes'):
         getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        getattr(lib, name).restype = ctypes.c_int64
+    for name in ('sgdfr_e4e_style_count', 'sgdfr_e4e_param_count'):      # a count, or -1 for a resolution out of range
+        getattr(lib, name).argtypes = [ctypes.c_int]
+        getattr(lib, name).restype = ctypes.c_int
+    lib.sgdfr_e4e_pack_elems.argtypes = [ctypes.c_int]
+    lib.sgdfr_e4e_pack_elems.restype = ctypes.c_int64
+    for name in ('sgdfr_e4e_debug_elems', 'sgdfr_e4e_workspace_bytes'):
+        getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int]
         getattr(lib, name).restype = ctypes.c_int64
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))

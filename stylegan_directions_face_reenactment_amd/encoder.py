@@ -17,13 +17,19 @@ specific to this build:
     filters on 8x8 ... 1x1 maps) are an unfold + one batched GEMM per depth, and the 14 `EqualLinear`s run on the HIP
     linear kernel (`sgdfr_linear_f32`);
   * like the reference (psp_encoders.py:185-199) no `latent_avg` is added; the generator applies truncation.
+
+Beside that, `encode(enc, images)` runs the whole encoder on the hand-written kernels of csrc/e4e.hip (exact-f32 MFMA implicit
+GEMM, forward only, one stream, no host synchronisation); `Encoder4Editing.forward` itself stays on the MIOpen plan.
 """
+import ctypes
 import math
+from collections import OrderedDict
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import _native as N
 from .model import EqualLinear
 
 # (depth, units) of the four trunk stages; the first unit of a stage has stride 2 (helpers.py:29-36, num_layers=50)
@@ -97,6 +103,7 @@ class Encoder4Editing(nn.Module):
             raise ValueError('num_layers should be 50, 100 or 152, got %r' % (num_layers,))
         if mode not in ('ir', 'ir_se'):
             raise ValueError("mode should be 'ir' or 'ir_se', got %r" % (mode,))
+        self.num_layers, self.mode, self.image_resolution = num_layers, mode, image_resolution
         self.input_layer = nn.Sequential(nn.Conv2d(3, 64, 3, 1, 1, bias=False), nn.BatchNorm2d(64), nn.PReLU(64))
         units, c = [], 64
         for depth, n in _TRUNK[num_layers]:
@@ -114,6 +121,7 @@ class Encoder4Editing(nn.Module):
         self.latlayer1 = nn.Conv2d(256, 512, 1)
         self.latlayer2 = nn.Conv2d(128, 512, 1)
         self._plan_key, self._plan = None, None
+        self._hip_pack = None       # (state key, device pack of csrc/e4e.hip, the folded tensors): see packed()
 
     # ------------------------------------------------------------------ reference-shaped (autograd-capable) forward
     def _features(self, x):
@@ -150,9 +158,15 @@ class Encoder4Editing(nn.Module):
         return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
     def invalidate_packs(self):
-        """Drop the folded inference plan (needed only after in-place `.data` edits, which the version counters behind
-        `_state_key` do not see)."""
+        """Drop the folded inference plan and the HIP weight pack (needed only after in-place `.data` edits, which the version
+        counters behind `_state_key` do not see)."""
         self._plan_key, self._plan = None, None
+        self._hip_pack = None
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state['_hip_pack'] = None       # rebuilt on demand: never copied, never pickled
+        return state
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
@@ -240,3 +254,131 @@ class Encoder4Editing(nn.Module):
             rows += [head.linear(h[:, j].contiguous()) for j, head in enumerate(heads)]
         w0 = rows[0]
         return torch.stack([w0] + [w0 + d for d in rows[1:]], dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- HIP path
+DEBUG_TAPS = ('stem', 'u0', 'u3', 'c1', 'c2', 'c3', 'p2', 'p1')       # then the head vectors h_coarse, h_middle, h_fine
+
+
+def _bn_affine(bn):
+    g = bn.weight.detach().double() * torch.rsqrt(bn.running_var.detach().double() + bn.eps)
+    return g, bn.bias.detach().double() - bn.running_mean.detach().double() * g
+
+
+def _fold64(conv, bn):
+    g, h = _bn_affine(bn)
+    return conv.weight.detach().double() * g.view(-1, 1, 1, 1), h
+
+
+def folded(enc, dtype=torch.float32):
+    """The tensors sgdfr_e4e_prepack_f32 takes, in the order include/sgdfr.h documents, every BatchNorm but BN1 folded into its
+    conv in fp64 (BN1 sits in front of a zero-padded conv: it travels as scale and shift).  None where a unit has no shortcut conv."""
+    out = list(_fold64(enc.input_layer[0], enc.input_layer[1])) + [enc.input_layer[2].weight.detach().double()]
+    for unit in enc.body:
+        r = unit.res_layer
+        out += list(_bn_affine(r[0])) + [r[1].weight.detach().double(), r[2].weight.detach().double()]
+        out += list(_fold64(r[3], r[4])) + [r[5].fc1.weight.detach().double().flatten(1), r[5].fc2.weight.detach().double().flatten(1)]
+        if isinstance(unit.shortcut_layer, nn.Sequential):
+            w, b = _fold64(unit.shortcut_layer[0], unit.shortcut_layer[1])
+            out += [w.flatten(1), b]
+        else:
+            out += [None, None]
+    for lat in (enc.latlayer1, enc.latlayer2):
+        out += [lat.weight.detach().double().flatten(1), lat.bias.detach().double()]
+    for head in enc.styles:
+        for m in head.convs:
+            if isinstance(m, nn.Conv2d):
+                out += [m.weight.detach().double(), m.bias.detach().double()]
+        lin = head.linear
+        if lin.activation is not None or lin.lr_mul != 1:
+            raise ValueError('encode: the style heads end in EqualLinear(512, 512, lr_mul=1) without activation')
+        out += [lin.weight.detach().double() * (1.0 / math.sqrt(lin.weight.shape[1])), lin.bias.detach().double()]
+    return [None if v is None else v.to(dtype).contiguous() for v in out]
+
+
+def _check_module(enc):
+    if not isinstance(enc, Encoder4Editing):
+        raise TypeError('encode: expected an Encoder4Editing, got %s' % type(enc).__name__)
+    if enc.mode != 'ir_se' or enc.num_layers != 50:
+        raise ValueError("encode: the HIP path runs Encoder4Editing(50, 'ir_se', R) only, got (%r, %r); use the module's own "
+                         'forward for the other trunks' % (enc.num_layers, enc.mode))
+    if enc.training:
+        raise RuntimeError('encode: the module is in train() mode; the HIP path folds the BatchNorm statistics, call .eval() first')
+    R = enc.image_resolution
+    if not isinstance(R, int) or R % 16 or not 32 <= R <= 256:
+        raise ValueError('encode: resolution %r is not a multiple of 16 in 32..256 (every style head must end at 1x1)' % (R,))
+    return R
+
+
+def packed(enc):
+    """The device weight pack of sgdfr_e4e_prepack_f32, rebuilt when any parameter's or buffer's storage or version changes."""
+    key = enc._state_key()
+    if enc._hip_pack is None or enc._hip_pack[0] != key:
+        R = enc.image_resolution
+        lib = N.load()
+        ps = folded(enc)
+        for p in ps:
+            N.require_device(p)
+        count = lib.sgdfr_e4e_param_count(R)
+        if count != len(ps) or lib.sgdfr_e4e_style_count(R) != enc.style_count:
+            raise RuntimeError('encode: %d folded tensors and %d heads, the kernels expect %d and %d at resolution %d' % (
+                len(ps), enc.style_count, count, lib.sgdfr_e4e_style_count(R), R))
+        pack = torch.empty(lib.sgdfr_e4e_pack_elems(R), dtype=torch.float32, device=enc.latlayer1.weight.device)
+        arr = (ctypes.c_void_p * count)(*[None if p is None else p.data_ptr() for p in ps])
+        N.call('sgdfr_e4e_prepack_f32', arr, R, N.ptr(pack), N.stream())
+        enc._hip_pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
+    return enc._hip_pack[1]
+
+
+def _workspace(rows, R, device):
+    nbytes = N.load().sgdfr_e4e_workspace_bytes(rows, R)
+    if nbytes < 0:
+        raise ValueError('encode: unsupported batch of %d images at resolution %d (1..256 rows, rows*R*R <= 2^24)' % (rows, R))
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+
+
+def debug_views(debug, rows, R, style_count):
+    """The debug buffer as named views (csrc/e4e.hip's DebugLayout): the eight feature taps, then the head vectors in front of the
+    EqualLinears as h_coarse [B,3,512], h_middle [B,4,512], h_fine [B,style_count-7,512]."""
+    shapes = (('stem', 64, R), ('u0', 64, R // 2), ('u3', 128, R // 4), ('c1', 128, R // 4), ('c2', 256, R // 8), ('c3', 512, R // 16),
+              ('p2', 512, R // 8), ('p1', 512, R // 4))
+    out, o = OrderedDict(), 0
+    for name, ch, side in shapes:
+        n = rows * ch * side * side
+        out[name] = debug[o:o + n].view(rows, ch, side, side)
+        o += n
+    h = debug[o:o + rows * style_count * 512].view(rows, style_count, 512)
+    o += h.numel()
+    assert o == debug.numel(), (o, debug.numel())
+    out['h_coarse'], out['h_middle'], out['h_fine'] = h[:, :3], h[:, 3:7], h[:, 7:]
+    return out
+
+
+def _encode(enc, images, debug):
+    R = _check_module(enc)
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+        raise ValueError('encode: expected [B,3,%d,%d] images, got %s' % (R, R, tuple(images.shape) if torch.is_tensor(images) else
+                                                                         type(images)))
+    if images.shape[2] != R or images.shape[3] != R:
+        raise ValueError('encode: images of %dx%d, the module was built for %dx%d' % (images.shape[2], images.shape[3], R, R))
+    N.require_device(images)
+    x = N.f32c(images.detach())
+    B = x.shape[0]
+    lib = N.load()
+    ws, nbytes = _workspace(B, R, x.device)
+    w = torch.empty((B, enc.style_count, 512), dtype=torch.float32, device=x.device)
+    dbg = torch.empty(lib.sgdfr_e4e_debug_elems(B, R), dtype=torch.float32, device=x.device) if debug else None
+    N.call('sgdfr_e4e_forward_f32', N.ptr(x), B, R, N.ptr(packed(enc)), N.ptr(w), N.ptr(dbg), N.ptr(ws), nbytes, N.stream())
+    return w, (None if dbg is None else debug_views(dbg, B, R, enc.style_count))
+
+
+def encode(enc, images):
+    """Encoder4Editing(50, 'ir_se', R) on the kernels of csrc/e4e.hip: images [B,3,R,R] float32 in [-1,1] on the device -> W+
+    [B,style_count,512].  Forward only (the result carries no graph), eval mode only, no CPU path, no host synchronisation."""
+    return _encode(enc, images, False)[0]
+
+
+def run_debug(enc, images):
+    """One pass with the debug taps -> dict: w [B,style_count,512] and debug (debug_views).  For tests."""
+    w, dbg = _encode(enc, images, True)
+    return {'w': w, 'debug': dbg}

@@ -85,6 +85,23 @@ def save_latent_codes(directory, names, latents):
     return paths
 
 
+@torch.no_grad()
+def invert_images(enc, G, images, truncation=1.0, trunc=None, as_uint8=False):
+    """The body of the reference's inversion loop (invert_images.py:101-125) as one call: images [B,3,R,R] in [-1,1] -> e4e W+
+    codes on the HIP encoder (encoder.encode) -> G([w], input_is_latent=True, truncation=..., truncation_latent=trunc).
+    Returns (latent_codes [B,n_latent,512], inverted frames [B,3,H,W] float32, or [B,H,W,3] uint8 with the reference's scaling
+    when as_uint8).  Encoder and generator share the caller's stream with no host synchronisation between them; the codes pair
+    with `save_latent_codes`."""
+    from .encoder import encode
+    if truncation < 1 and trunc is None:
+        raise RuntimeError('truncation < 1 needs the truncation latent')
+    w = encode(enc, images)
+    if w.shape[1] != G.n_latent:
+        raise RuntimeError('invert_images: the encoder gives %d latents, the generator takes %d' % (w.shape[1], G.n_latent))
+    frames, _ = G([w], input_is_latent=True, truncation=truncation, truncation_latent=trunc)
+    return w, (images_to_uint8(frames) if as_uint8 else frames)
+
+
 def load_latent_codes(paths, device=None):
     """Read per-frame `.npy` codes back into one [B,n_latent,512] tensor (pinned staging, one H2D copy)."""
     codes = [np.load(p) for p in paths]
