@@ -20,15 +20,26 @@ COARSE, MIDDLE = 3, 7
 CASES = OrderedDict([('a', (3, 64, SEED + 1, 'e4e.x64')), ('b', (2, 96, SEED + 2, 'e4e.x96')), ('c', (2, 256, SEED, 'e4e.x'))])
 
 
+# the plan sweep (tests/test_gpu_s3fd_e4e_plans.py): resolution -> case name.  64, 96 and 256 are the fixture cases; the others are
+# seeded here in the same way and exist in no fixture: their yardstick is the fp32 restatement's own deviation from the fp64 one.
+SWEEP_CASES = OrderedDict([('r32', (2, 32, SEED + 32, 'e4e.plan.x32')), ('r48', (3, 48, SEED + 48, 'e4e.plan.x48')),
+                           ('r80', (2, 80, SEED + 80, 'e4e.plan.x80')), ('r128', (3, 128, SEED + 128, 'e4e.plan.x128'))])
+SWEEP = OrderedDict([(32, 'r32'), (48, 'r48'), (64, 'a'), (80, 'r80'), (96, 'b'), (128, 'r128'), (256, 'c')])
+
+
+def case(name):
+    return CASES[name] if name in CASES else SWEEP_CASES[name]
+
+
 def fixture_inputs(S, name):
     """Images [B,3,R,R] float32 in [-1,1] of a fixture case, regenerated from its counter key."""
-    B, R, _, key = CASES[name]
+    B, R, _, key = case(name)
     return S.counter_tensor(SEED, key, (B, 3, R, R), 0.0, 0.5).clamp_(-1, 1)
 
 
 def fixture_state(S, name, template):
     """The seeded state of a fixture case; `template` is a state dict with the module's keys and shapes at that resolution."""
-    return S.synthetic_encoder_state(template, seed=CASES[name][2])
+    return S.synthetic_encoder_state(template, seed=case(name)[2])
 
 
 def _bn(P, k, x):

@@ -1,0 +1,207 @@
+"""The split-K plan rules and launch lists of csrc/e4e.hip and csrc/s3fd.hip restated in plain Python (no GPU, no library call):
+which convs a forward pass launches at a given size, and into how many K slices the host code cuts each of them.  A conv with S > 1
+slices runs its epilogue in the finish kernel, one with S = 1 ("whole") in the conv kernel itself, so the number of finish launches
+of a pass is the number of launches with S > 1.  tests/test_cpu_e4e_taps.py and tests/test_cpu_s3fd.py pin the geometry to the C
+ABI and assert the coverage condition over the cases listed here; tests/test_gpu_s3fd_e4e_plans.py runs those cases and compares
+the profiler's launch counts with `e4e_counts` / `s3fd_counts`."""
+from collections import OrderedDict, namedtuple
+
+Launch = namedtuple('Launch', 'cls name G N Ho Wo K')
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def _rederive(chunks, S):
+    S = max(1, min(S, 32))
+    cps = _ceil(chunks, S)
+    return _ceil(chunks, cps)
+
+
+# ---------------------------------------------------------------------------------------------------------------- e4e
+E4E_SPLIT_BELOW = 192
+E4E_MAX_ROWS = 256
+
+
+def e4e_slices(B, G, N, Ho, Wo, K):
+    """plan_conv of csrc/e4e.hip: 64 x 64 tiles, whole from 192 tiles on, else at most 512 / tiles slices of at least 8 chunks."""
+    tiles = _ceil(B * Ho * Wo, 64) * _ceil(N, 64) * G
+    chunks = _ceil(K, 16)
+    S = 1 if tiles >= E4E_SPLIT_BELOW else min(512 // max(tiles, 1), chunks // 8)
+    return _rederive(chunks, S)
+
+
+def e4e_style_count(R):
+    l = 0
+    while (2 << l) <= R:
+        l += 1                          # floor(log2 R)
+    return 2 * l - 2
+
+
+def e4e_units(R):
+    """(cin, depth, stride, h, ho, has shortcut conv) of the 24 units."""
+    out, c, h = [], 64, R
+    for depth, count in ((64, 3), (128, 4), (256, 14), (512, 3)):
+        for k in range(count):
+            stride = 2 if k == 0 else 1
+            ho = (h - 1) // stride + 1
+            out.append((c, depth, stride, h, ho, c != depth))
+            c, h = depth, ho
+    return out
+
+
+def e4e_groups(R):
+    """(first head, one past the last, convs per head, side of the input map) of the three head groups."""
+    return ((0, 3, 4, R // 16), (3, 7, 5, R // 8), (7, e4e_style_count(R), 6, R // 4))
+
+
+def live_taps(side):
+    """The filter positions of a 3 x 3 / stride 2 / pad 1 conv on a side x side map that meet the map for some output pixel."""
+    so = (side - 1) // 2 + 1
+    live = [any(0 <= 2 * o - 1 + k < side for o in range(so)) for k in range(3)]
+    return [kh * 3 + kw for kh in range(3) for kw in range(3) if live[kh] and live[kw]]
+
+
+def e4e_launches(R):
+    """Every e4e_conv_kernel launch of one forward pass at resolution R, in launch order.  K counts the live taps only."""
+    out = [Launch('stem', 'stem', 1, 64, R, R, 27)]
+    for i, (cin, d, stride, h, ho, sc) in enumerate(e4e_units(R)):
+        out.append(Launch('conv1', 'u%d.conv1' % i, 1, d, h, h, cin * 9))
+        out.append(Launch('conv2_s%d' % stride, 'u%d.conv2' % i, 1, d, ho, ho, d * 9))
+        if sc:
+            out.append(Launch('shortcut', 'u%d.shortcut' % i, 1, d, ho, ho, cin))
+    out.append(Launch('lateral', 'latlayer1', 1, 512, R // 8, R // 8, 256))
+    out.append(Launch('lateral', 'latlayer2', 1, 512, R // 4, R // 4, 128))
+    for g, (lo, hi, depth, side) in enumerate(e4e_groups(R)):
+        G = hi - lo
+        for k in range(depth):
+            so = (side - 1) // 2 + 1
+            K = 512 * len(live_taps(side))
+            if k == 0:
+                out.append(Launch('head_first', 'g%d.k0' % g, 1, G * 512, so, so, K))
+            elif k == depth - 1:
+                assert so == 1, (R, g, so)
+                out.append(Launch('head_last', 'g%d.k%d' % (g, k), G, 512, so, so, K))
+            else:
+                out.append(Launch('head_grouped' if G > 1 else 'head_single', 'g%d.k%d' % (g, k), G, 512, so, so, K))
+            side = so
+    out.append(Launch('linear', 'linear', e4e_style_count(R), 512, 1, 1, 512))
+    return out
+
+
+def e4e_plan(B, R):
+    return [(l, e4e_slices(B, l.G, l.N, l.Ho, l.Wo, l.K)) for l in e4e_launches(R)]
+
+
+def e4e_counts(B, R):
+    """(conv launches, finish launches) of one forward pass."""
+    plan = e4e_plan(B, R)
+    return len(plan), sum(S > 1 for _, S in plan)
+
+
+E4E_CLASSES = ('stem', 'conv1', 'conv2_s1', 'conv2_s2', 'shortcut', 'lateral', 'head_first', 'head_grouped', 'head_single',
+               'head_last', 'linear')
+# (class, 'sliced' or 'whole') that no case can show, each with its reason; test_cpu_e4e_taps proves the reasons
+E4E_EXCEPTIONS = OrderedDict([
+    (('stem', 'sliced'), 'K = 27 is two chunks of 16: never eight chunks per slice, whole at every size'),
+])
+# the GPU cases of tests/test_gpu_s3fd_e4e_plans.py: (R, B).  Small batches of distinct images at every resolution, then batches
+# of repeated rows: (64, 96) and (64, 192) run unit 21's shortcut, the lateral convs, the grouped head convs and (192) the
+# EqualLinears whole; (48, 192) runs group 2's single-head convs whole (9 B pixels of a 3 x 3 map: from B = 164 on); (256, 194)
+# runs the last head conv whole (7 heads x 8 channel tiles x ceil(B / 64) >= 192 only with 7 heads, i.e. R = 256, and B >= 193).
+E4E_SMALL = ((32, 2), (48, 3), (64, 3), (80, 2), (96, 2), (128, 3))
+E4E_LARGE = ((64, 96), (64, 192), (48, 192), (256, 194))
+
+
+def coverage(plans, classes):
+    """{(class, 'sliced' | 'whole')} seen over plans = iterables of (launch, S)."""
+    seen = set()
+    for plan in plans:
+        for l, S in plan:
+            assert l.cls in classes, l
+            seen.add((l.cls, 'sliced' if S > 1 else 'whole'))
+    return seen
+
+
+# ---------------------------------------------------------------------------------------------------------------- S3FD
+# (name, cin, cout, kernel, stride, pad, a pool follows, level fed)
+S3FD_NET = (('conv1_1', 3, 64, 3, 1, 1, 0, -1), ('conv1_2', 64, 64, 3, 1, 1, 1, -1), ('conv2_1', 64, 128, 3, 1, 1, 0, -1),
+            ('conv2_2', 128, 128, 3, 1, 1, 1, -1), ('conv3_1', 128, 256, 3, 1, 1, 0, -1), ('conv3_2', 256, 256, 3, 1, 1, 0, -1),
+            ('conv3_3', 256, 256, 3, 1, 1, 1, 0), ('conv4_1', 256, 512, 3, 1, 1, 0, -1), ('conv4_2', 512, 512, 3, 1, 1, 0, -1),
+            ('conv4_3', 512, 512, 3, 1, 1, 1, 1), ('conv5_1', 512, 512, 3, 1, 1, 0, -1), ('conv5_2', 512, 512, 3, 1, 1, 0, -1),
+            ('conv5_3', 512, 512, 3, 1, 1, 1, 2), ('fc6', 512, 1024, 3, 1, 3, 0, -1), ('fc7', 1024, 1024, 1, 1, 0, 0, 3),
+            ('conv6_1', 1024, 256, 1, 1, 0, 0, -1), ('conv6_2', 256, 512, 3, 2, 1, 0, 4), ('conv7_1', 512, 128, 1, 1, 0, 0, -1),
+            ('conv7_2', 128, 256, 3, 2, 1, 0, 5))
+S3FD_HEAD_C = (256, 512, 512, 1024, 512, 256)
+S3FD_HEAD_CONF = (4, 2, 2, 2, 2, 2)
+S3FD_MAX_ROWS = 256
+S3FD_MAX_PIXELS = 1 << 24
+
+
+def s3fd_slices(B, N, Ho, Wo, K, bn):
+    """plan_conv of csrc/s3fd.hip: 64-pixel tiles of `bn` channels, at most 512 / tiles slices of at least 8 chunks."""
+    tiles = _ceil(B * Ho * Wo, 64) * _ceil(N, bn)
+    chunks = _ceil(K, 16)
+    return _rederive(chunks, min(512 // max(tiles, 1), chunks // 8))
+
+
+def s3fd_level_dims(H, W):
+    dims, h, w = [None] * 6, H, W
+    for _, _, _, ks, stride, pad, pool, level in S3FD_NET:
+        h, w = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+        if level >= 0:
+            dims[level] = (h, w)
+        if pool:
+            h, w = h // 2, w // 2
+    return dims
+
+
+def s3fd_launches(H, W):
+    """(launch, channel tile) of the 25 s3fd_conv_kernel launches of one pass over H x W images, in launch order."""
+    out, h, w = [], H, W
+    for name, cin, cout, ks, stride, pad, pool, _ in S3FD_NET:
+        h, w = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+        cls = 'fc6' if pad == 3 else 'stride2' if stride == 2 else 'one' if ks == 1 else 'trunk3_pool' if pool else 'trunk3'
+        out.append((Launch(cls, name, 1, cout, h, w, cin * ks * ks), 64))
+        if pool:
+            h, w = h // 2, w // 2
+    for l, (lh, lw) in enumerate(s3fd_level_dims(H, W)):
+        out.append((Launch('head_rn' if l < 3 else 'head', 'head%d' % l, 1, S3FD_HEAD_CONF[l] + 4, lh, lw, 9 * S3FD_HEAD_C[l]), 16))
+    return out
+
+
+def s3fd_plan(B, H, W):
+    return [(l, s3fd_slices(B, l.N, l.Ho, l.Wo, l.K, bn)) for l, bn in s3fd_launches(H, W)]
+
+
+def s3fd_counts(B, H, W):
+    plan = s3fd_plan(B, H, W)
+    return len(plan), sum(S > 1 for _, S in plan)
+
+
+S3FD_CLASSES = ('trunk3', 'trunk3_pool', 'one', 'stride2', 'fc6', 'head_rn', 'head')
+S3FD_EXCEPTIONS = OrderedDict()         # every class runs sliced and whole within 256 rows and 2^24 pixels
+# the GPU cases: name -> (B, H, W, subtract_mean, image seeds).  A batch holds the distinct images of its seeds (one image per seed,
+# tests/s3fd_restatement.py plan_images), repeated in a permuted order up to B rows.  32 x 32 is the smallest legal image; at 63 x 95
+# every pool drops a row and a column, and 47 x 63 (with the mean subtraction) is odd as well; the 128 x 128 batches are the first
+# at which conv5_x, fc6, fc7 and the level-0 head (B = 33) and conv6_1 and the level-1 head (B = 65) run whole.  conv6_2 and a head
+# without the L2Norm factor run whole only when their own map has more than 256 pixel tiles, i.e. more than 16384 fc7 pixels in
+# the batch: the 8 x 8 fc7 map of 128 x 128 would need 257 rows, the 5 x 14 map of a 32 x 320 strip needs 235 (and has few enough
+# candidates for a decisive image to exist).  The seeds are the first for which the fp64 restatement's decisions are decisive
+# (test_cpu_s3fd.test_plan_cases_are_decisive).
+S3FD_CASES = OrderedDict([
+    ('tiny', (1, 32, 32, False, (1,))),
+    ('odd', (2, 63, 95, False, (2, 3))),
+    ('mean', (1, 47, 63, True, (1,))),
+    ('b33', (33, 128, 128, False, (101, 153, 203))),
+    ('b65', (65, 128, 128, False, (101, 153, 203))),
+    ('b240', (240, 32, 320, False, (2, 3))),
+])
+
+
+def batch_rows(B, n):
+    """Which distinct image each of B rows holds: every image about B / n times, in an order that is no period of the 64-pixel tile."""
+    rows = [(i * 7 + i // n) % n for i in range(B)] if B > n else list(range(B))
+    assert set(rows) == set(range(min(B, n)))
+    return rows

@@ -214,3 +214,161 @@ def maps_of_heads(heads):
             c = torch.cat([c[:, :3].max(1, keepdim=True).values, c[:, 3:]], 1)
         maps += [c, t[:, conf:]]
     return maps
+
+
+# ---------------------------------------------------------------------------------------------------------------- decisive cases
+def decisive_reference(state, x, subtract_mean=False):
+    """What a comparison of decisions at a new size needs, from the restatement alone: the fp64 and fp32 taps and maps on the CPU,
+    per tensor dev = max |fp32 - fp64| (the yardstick of the 8 x bars; dev_cand over the candidate lists, dev_boxes over the final
+    boxes), per image the fp64 candidate list and selection, and the
+    margins that make exact comparison of the decisions fair (those scripts/make_golden_s3fd.py asserts for the fixture):
+    gap_cut = the smallest |score - cut| / (score dev of its level) over every position and both cuts 0.05 and 0.5, gap_adjacent =
+    the same for neighbours in the sorted list above 0.5 of which at least one is kept (a run of near-tied boxes that are all
+    suppressed is suppressed by kept boxes ranked above the whole run, whatever the order inside it, and suppresses nothing itself:
+    the order inside such a run decides nothing), near_iou = the smallest |IoU - 0.3| the greedy pass compares in either
+    precision, agree = the fp32 restatement takes the fp64 decisions."""
+    with torch.no_grad():
+        t64, t32 = network(state, x.double(), subtract_mean), network(state, x, subtract_mean)
+    dev = {k: float((t32[k].double() - t64[k]).abs().max()) for k in TAPS}
+    dev_maps = [float((a.double() - b).abs().max()) for a, b in zip(t32['maps'], t64['maps'])]
+    s64, s32 = scores_of(t64['maps']), scores_of(t32['maps'])
+    dev_s = [float((s32[l].double() - s64[l]).abs().max()) for l in range(LEVELS)]
+    gap_cut = min(float((s64[l] - cut).abs().min()) / dev_s[l] for l in range(LEVELS) for cut in (0.05, 0.5))
+    images_out, gap_adj, near, agree, dev_boxes, dev_cand = [], float('inf'), float('inf'), True, 0.0, 0.0
+    for b in range(x.shape[0]):
+        d64, d32 = decode_image(t64['maps'], b), decode_image(t32['maps'], b)
+        agree = agree and all(np.array_equal(d64[k], d32[k]) for k in ('level', 'y', 'x'))
+        dets = d64['dets']
+        if agree and len(dets):
+            dev_cand = max(dev_cand, float(np.abs(d32['dets'].astype(np.float64) - dets).max()))
+        order, keep, compared = greedy_nms(dets)
+        compared32 = greedy_nms(d32['dets'])[2] if len(d32['dets']) else []
+        near = min([near] + [abs(v - 0.3) for c in (compared, compared32) for _, _, v in c])
+        kept, boxes = select(dets, floor=0.5)
+        kept32, boxes32 = select(d32['dets'], floor=0.5)
+        agree = agree and kept == kept32 and kept == select(dets)[0]
+        if agree and kept:
+            dev_boxes = max(dev_boxes, float(np.abs(boxes32.astype(np.float64) - boxes).max()))
+        hi = [i for i in order if dets[i, 4] > 0.5]
+        dl = np.array(dev_s)[d64['level']]
+        for i, j in zip(hi[:-1], hi[1:]):
+            if i in kept or j in kept:
+                gap_adj = min(gap_adj, float(dets[i, 4] - dets[j, 4]) / max(dl[i], dl[j]))
+        images_out.append({'dets': dets, 'kept': kept, 'boxes': boxes, 'above': len(hi)})
+    return {'taps64': t64, 'dev': dev, 'dev_maps': dev_maps, 'dev_scores': dev_s, 'dev_boxes': dev_boxes, 'dev_cand': dev_cand, 'images': images_out,
+            'gap_cut': gap_cut, 'gap_adjacent': gap_adj, 'near_iou': near, 'agree': agree,
+            'max_loc': max(float(m.abs().max()) for m in t64['maps'][1::2])}
+
+
+# ---------------------------------------------------------------------------------------------------------------- long lists
+NMS_CAPACITY = 1024
+NMS_SEED = 1          # the first seed for which every IoU the greedy passes compare is 1e-3 away from 0.3 (test_cpu_s3fd asserts it)
+
+
+def _grid_boxes(rng, cells, side=64.0, size=40.0):
+    """One float32 box per entry of `cells` (indices into a 48 x 48 grid of `side`-pixel cells), jittered inside its cell: boxes of
+    different cells never touch, boxes of one cell overlap at a random IoU."""
+    cells = np.asarray(cells)
+    x = (cells % 48) * side + rng.uniform(0, side - size - 2, len(cells))
+    y = (cells // 48) * side + rng.uniform(0, side - size - 2, len(cells))
+    w, h = rng.uniform(0.7 * size, size, len(cells)), rng.uniform(0.7 * size, size, len(cells))
+    return np.stack([x, y, x + w, y + h], 1).astype(np.float32)
+
+
+def nms_rows(seed=NMS_SEED):
+    """Candidate lists that use every part of s3fd_nms_kernel at capacity 1024 -> OrderedDict name -> (cand [n,5] float32, count).
+    many: 800 boxes, 540 above 0.5 (300 alone in their cell, 240 sharing a cell with one of them), 260 at or below 0.5 in between.
+    clusters: three clusters of 250 near-copies and 30 boxes apart: the best of a cluster suppresses hundreds, spread over all ranks.
+    ties: 300 boxes with scores on a coarse grid, then 150 exact copies (box and score) and 150 boxes elsewhere with the same score,
+    each 300 places behind its twin: the lower index wins, and comes first.
+    over: a full list whose count says 1500.  none: a count of 0 in front of a list that is not empty."""
+    rng = np.random.RandomState(seed)
+    rows = OrderedDict()
+    # many
+    own = rng.permutation(48 * 48)[:300]
+    cells = np.concatenate([own, rng.choice(own, 240), rng.permutation(48 * 48)[:260]])
+    score = np.concatenate([rng.uniform(0.51, 0.999, 540), rng.uniform(0.06, 0.5, 260)]).astype(np.float32)
+    score[539] = 0.5                                          # exactly 0.5 does not pass
+    mix = rng.permutation(800)
+    rows['many'] = (np.concatenate([_grid_boxes(rng, cells), score[:, None]], 1).astype(np.float32)[mix], 800)
+    # clusters
+    centre = _grid_boxes(rng, rng.permutation(48 * 48)[:3], size=60.0)
+    near = np.repeat(centre, 250, 0) + rng.randint(-2, 3, (750, 4)).astype(np.float32)
+    apart = _grid_boxes(rng, 1000 + rng.permutation(1000)[:30])
+    boxes = np.concatenate([near, apart])
+    score = rng.uniform(0.55, 0.999, len(boxes)).astype(np.float32)
+    mix = rng.permutation(len(boxes))
+    rows['clusters'] = (np.concatenate([boxes, score[:, None]], 1).astype(np.float32)[mix], len(boxes))
+    # ties
+    base = _grid_boxes(rng, rng.permutation(1100)[:300])
+    sc = (0.55 + rng.randint(0, 24, 300) / 64.0).astype(np.float32)
+    other = _grid_boxes(rng, 1200 + rng.permutation(1000)[:300])
+    twin = np.where((np.arange(300) % 2 == 0)[:, None], base, other)
+    rows['ties'] = (np.concatenate([np.concatenate([base, twin]), np.concatenate([sc, sc])[:, None]], 1).astype(np.float32), 600)
+    # over: 1024 rows, clustered so that the Python pass stays short
+    centre = _grid_boxes(rng, rng.permutation(48 * 48)[:40], size=60.0)
+    boxes = np.repeat(centre, 25, 0) + rng.randint(-2, 3, (1000, 4)).astype(np.float32)
+    boxes = np.concatenate([boxes, _grid_boxes(rng, rng.permutation(48 * 48)[:24])])
+    score = rng.uniform(0.3, 0.999, NMS_CAPACITY).astype(np.float32)
+    mix = rng.permutation(NMS_CAPACITY)
+    rows['over'] = (np.concatenate([boxes, score[:, None]], 1).astype(np.float32)[mix], 1500)
+    rows['none'] = (rows['ties'][0][:100].copy(), 0)
+    return rows
+
+
+def nms_wide(seed=NMS_SEED):
+    """300 boxes for a list of capacity 16384."""
+    rng = np.random.RandomState(seed + 1000)
+    own = rng.permutation(48 * 48)[:200]
+    boxes = _grid_boxes(rng, np.concatenate([own, rng.choice(own, 100)]))
+    score = rng.uniform(0.3, 0.999, 300).astype(np.float32)
+    return np.concatenate([boxes, score[:, None]], 1).astype(np.float32)[rng.permutation(300)]
+
+
+def nms_reference(dets, count, capacity=NMS_CAPACITY):
+    """select() over what the kernel sees of a row -> (kept indices, boxes, smallest |IoU - 0.3| compared, candidates above 0.5)."""
+    dets = dets[:min(max(count, 0), capacity)]
+    ids = np.nonzero(dets[:, 4] > 0.5)[0]
+    _, keep, compared = greedy_nms(dets[ids])
+    kept = [int(ids[i]) for i in keep]
+    near = min([1.0] + [abs(v - 0.3) for _, _, v in compared])
+    return kept, (dets[kept] if kept else np.zeros((0, 5), dtype=dets.dtype)), near, len(ids)
+
+
+PLAN_DIMS = ((32, 32), (16, 16), (8, 8), (8, 8), (4, 4), (2, 2))          # the level maps of a 128 x 128 image: 1428 positions
+
+
+def long_heads(seed=3):
+    """Raw head outputs [3, conf+4, h, w] at PLAN_DIMS, six chunks of 256 positions per image.  Image 0: every position of chunk 0
+    passes (level 0, rows 0-7), no position of chunk 2 (level 0, rows 16-23), a random third of every other position: chunks 1 and 3
+    on level 0, chunk 4 (level 1) and the last, partial chunk (levels 2-5).  Image 1: a random quarter
+    everywhere.  Image 2 passes nowhere.  Logits are
+    multiples of 1/8 with face - background in {-6} (score 0.0025), {-2} (0.12, passes 0.05 only) or 0..3 (0.5 .. 0.95)."""
+    rng = np.random.RandomState(seed)
+    heads = []
+    for l, (h, w) in enumerate(PLAN_DIMS):
+        conf = 4 if l == 0 else 2
+        t = torch.zeros(3, conf + 4, h, w)
+        n = h * w
+        for b in range(3):
+            if b == 0:
+                p = rng.uniform(size=n) < 1.0 / 3
+                if l == 0:
+                    p[:256], p[512:768] = True, False
+            else:
+                p = rng.uniform(size=n) < (0.25 if b == 1 else 0.0)
+            gap = np.where(p, np.where(rng.uniform(size=n) < 0.3, -2.0, rng.randint(0, 25, n) / 8.0), -6.0)
+            top = rng.randint(-8, 9, n) / 8.0                                   # the largest background logit
+            bg = top[None, :] - rng.randint(0, 17, (conf - 1, n)) / 8.0
+            which = rng.randint(0, conf - 1, n)
+            bg[which, np.arange(n)] = top
+            t[b, :conf - 1] = torch.from_numpy(bg).float().view(conf - 1, h, w)
+            t[b, conf - 1] = torch.from_numpy(top + gap).float().view(h, w)
+            t[b, conf:] = torch.from_numpy(rng.randint(-12, 13, (4, n)) / 8.0).float().view(4, h, w)
+        heads.append(t)
+    return heads
+
+
+def plan_images(S, H, W, seeds):
+    """The distinct images of a plan-sweep case (tests/plan_rules.py S3FD_CASES): one seeded image per seed."""
+    return torch.cat([images(S, seed, 's3fd.plan.%dx%d' % (H, W), 1, H, W) for seed in seeds])

@@ -32,7 +32,7 @@ def make_encoder(name):
 
 def _make_encoder(name):
     from stylegan_directions_face_reenactment_amd.encoder import Encoder4Editing
-    enc = Encoder4Editing(50, 'ir_se', R.CASES[name][1]).eval()
+    enc = Encoder4Editing(50, 'ir_se', R.case(name)[1]).eval()
     state = R.fixture_state(S, name, enc.state_dict())
     enc.load_state_dict(state, strict=True)
     return enc, state
@@ -156,3 +156,64 @@ def test_pack_stays_out_of_the_state_dict_copies_and_pickles(small):
         assert enc._hip_pack is None
     finally:
         enc._hip_pack = None
+
+
+# ---------------------------------------------------------------------------------------------------------------- the plan rules
+def test_plan_rule_geometry_matches_the_c_abi():
+    """tests/plan_rules.py restates the geometry csrc/e4e.hip plans from: the head count at every resolution the ABI admits, the
+    live taps of the head convs, and the launch total the GPU tests assert."""
+    import plan_rules as P
+    from stylegan_directions_face_reenactment_amd import _native
+    lib = _native.load()
+    for res in range(32, 257, 16):
+        assert P.e4e_style_count(res) == lib.sgdfr_e4e_style_count(res), res
+        groups = P.e4e_groups(res)
+        assert [hi - lo for lo, hi, _, _ in groups] == [3, 4, P.e4e_style_count(res) - 7]
+        for lo, hi, depth, side in groups:                  # every head ends at 1 x 1 after its 4 / 5 / 6 convs
+            for _ in range(depth):
+                side = (side - 1) // 2 + 1
+            assert side == 1, res
+    assert all(res in R.SWEEP for res, _ in P.E4E_SMALL + P.E4E_LARGE)
+    assert [R.case(R.SWEEP[res])[:2] for res, _ in P.E4E_SMALL] == [(B, res) for res, B in P.E4E_SMALL]
+    # one tap of a 1 x 1 map, four of 2 x 2, all nine from 3 x 3 on (an odd map reaches its last row through tap 0 of the next output)
+    assert [len(P.live_taps(s)) for s in (1, 2, 3, 4, 5, 7, 8)] == [1, 4, 9, 9, 9, 9, 9]
+    assert P.live_taps(1) == [4] and P.live_taps(2) == [4, 5, 7, 8]
+    # R = 80: 5 -> 3 -> 2 -> 1 -> 1; R = 112: 7 -> 4 -> 2 -> 1 -> 1 (K = 512 x taps of the input map)
+    assert [l.K // 512 for l in P.e4e_launches(80) if l.name.startswith('g0.')] == [9, 9, 4, 1]
+    assert [l.K // 512 for l in P.e4e_launches(112) if l.name.startswith('g0.')] == [9, 9, 4, 1]
+    assert [l.K // 512 for l in P.e4e_launches(64) if l.name.startswith('g0.')] == [9, 4, 1, 1]
+    for res in range(32, 257, 16):
+        assert len(P.e4e_launches(res)) == 1 + 48 + 3 + 2 + 15 + 1 == 70
+    assert P.e4e_counts(3, 64)[0] == 70
+    # what the existing GPU test observes at R = 64: fewer sliced convs as the batch grows, one fewer at B = 3 (unit 0's conv1)
+    f = [P.e4e_counts(B, 64)[1] for B in (1, 2, 3)]
+    assert f[0] >= f[1] >= f[2] > 0 and f[0] > f[2], f
+
+
+def test_sweep_cases_cover_every_launch_class_sliced_and_whole():
+    """The coverage condition: over the GPU cases of test_gpu_s3fd_e4e_plans every launch class of csrc/e4e.hip runs at least once
+    sliced over K (epilogue in e4e_finish_kernel) and at least once whole (epilogue in e4e_conv_kernel).  The exceptions are named
+    in plan_rules.E4E_EXCEPTIONS and proven here over every size the ABI admits."""
+    import plan_rules as P
+    cases = P.E4E_SMALL + P.E4E_LARGE
+    assert all(1 <= B <= P.E4E_MAX_ROWS and B * res * res <= 1 << 24 for res, B in cases)
+    seen = P.coverage([P.e4e_plan(B, res) for res, B in cases], P.E4E_CLASSES)
+    want = {(c, how) for c in P.E4E_CLASSES for how in ('sliced', 'whole')}
+    for res, B in cases:
+        plan = P.e4e_plan(B, res)
+        sliced, whole = [l.name for l, S in plan if S > 1], [l.name for l, S in plan if S == 1]
+        print('R = %3d B = %3d: %d convs, %d sliced; %s' % (res, B, len(plan), len(sliced), 'whole: ' + ' '.join(whole)
+                                                            if len(whole) <= len(sliced) else 'sliced: ' + ' '.join(sliced)))
+    print('exceptions: %s' % '; '.join('%s never %s (%s)' % (c, how, why) for (c, how), why in P.E4E_EXCEPTIONS.items()))
+    assert want - seen == set(P.E4E_EXCEPTIONS), sorted(want - seen)
+    assert list(P.E4E_EXCEPTIONS) == [('stem', 'sliced')]
+    reach = P.coverage([P.e4e_plan(B, res) for res in range(32, 257, 16) for B in range(1, P.E4E_MAX_ROWS + 1) if B * res * res <= 1 << 24],
+                       P.E4E_CLASSES)
+    assert not (set(P.E4E_EXCEPTIONS) & reach)              # no admitted size reaches an exception ...
+    assert reach == seen                                    # ... and the cases reach everything an admitted size can
+    # the paths the small fixtures never ran, by name: unit 21's SE-gated shortcut and the grouped launches run whole
+    whole = {(res, B): {l.name for l, S in P.e4e_plan(B, res) if S == 1} for res, B in cases}
+    assert 'u21.shortcut' not in whole[(64, 3)] and 'u21.shortcut' in whole[(64, 96)]
+    assert 'linear' not in whole[(64, 96)] and 'linear' in whole[(64, 192)]
+    assert {'g1.k1', 'g2.k1'} <= whole[(64, 96)] and 'g2.k1' in whole[(48, 192)] and {'g0.k3', 'g1.k4'} & whole[(256, 194)] == set()
+    assert 'g2.k5' in whole[(256, 194)]
