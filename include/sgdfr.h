@@ -788,6 +788,33 @@ int sgdfr_e4e_prepack_f32(const float* const* params, int R, float* pack, void* 
 int sgdfr_e4e_forward_f32(const float* x, int rows, int R, const float* pack, float* w, float* debug, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* The FFHQ alignment crop in front of the e4e encoder (libs/face_models/ffhq_cropping.py:13-69 crop_using_landmarks with
+ * pad_img_to_fit_bbox and crop_from_bbox), csrc/facecrop.hip.  frames [rows,H,W,3] uint8, landmarks [rows,68,2] fp32, both on the
+ * device; 1..1024 rows, H, W and max_size in 1..4096, out_size S in 1..1024.
+ * Box, in the reference's integer semantics: centre = round((min + max) / 2) in fp32, half to even; size = (int) max(extent_x,
+ *   extent_y); centre_y -= size / 6; box = centre -+ size.  boxes [rows,4] = x1, y1, x2, y2 and sizes [rows] (zeros for landmarks
+ *   that are not finite or lie beyond 1e6).
+ * valid [rows] = 0 where size < 1, size > max_size (the workspace's capacity), a border is wider than the frame dimension it reflects
+ *   (the reference's border repeats there; this is the one deviation) or the padded frame would exceed the workspace (a box far
+ *   outside the frame); such a row's crop is zeros (and its e4e row 0.0) and no other row is affected.
+ * Rows whose box leaves the frame: symmetric border (cv2.BORDER_REFLECT), the feather mask from the four border widths with 1e-10
+ *   for a zero width, scipy's separable Gaussian (sigma 5, 41 taps, 'reflect', axis 0 then axis 1, double weights and accumulator,
+ *   fp32 after each axis) over the whole padded frame, img += (blur - img) * clip(3 mask + 1, 0, 1), the per-channel np.median of
+ *   the padded frame as an exact selection (integer atomics: reproducible), img += (median - img) * clip(mask, 0, 1), truncation to
+ *   uint8.  Rows whose box is inside the frame go straight to the resize.
+ * Resize: Pillow's 8-bit bicubic resampler (Resample.c: coefficients in double, 22-bit integers, horizontal pass, uint8, vertical
+ *   pass), bit-exact, with the coefficients of each row's crop side 2 size computed on the device.
+ * crops [rows,S,S,3] uint8; e4e (NULL: off) [rows,3,S,S] fp32 = u8 / 255 * 2 - 1 in that fp32 order; boxes and sizes may be NULL;
+ *   crop_float (NULL: off) receives rows * (2 max_size)^2 * 3 floats: per row, at offset row * (2 max_size)^2 * 3, the dense
+ *   [2 size, 2 size, 3] crop in front of the truncation.
+ * workspace: device scratch of at least sgdfr_facecrop_workspace_bytes(rows, H, W, max_size) bytes (-1 for sizes out of range).
+ * Deterministic, no host synchronisation, everything on `stream`. */
+int64_t sgdfr_facecrop_workspace_bytes(int rows, int H, int W, int max_size);
+int sgdfr_facecrop_boxes_f32(const float* landmarks, int rows, int* boxes, int* sizes, void* stream);
+int sgdfr_facecrop_forward_u8(const uint8_t* frames, const float* landmarks, int rows, int H, int W, int out_size, int max_size,
+                              uint8_t* crops, int* valid, float* e4e, int* boxes, int* sizes, float* crop_float, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

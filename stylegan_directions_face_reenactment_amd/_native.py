@@ -206,6 +206,10 @@ SIGNATURES['sgdfr_s3fd_forward_f32'] = [_c_f32p, _i, _i, _i, _i, _c_f32p, _f, _i
 S3FD_PARAMS = 50        # pointers sgdfr_s3fd_prepack_f32 takes
 SIGNATURES['sgdfr_e4e_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _i, _c_f32p, ctypes.c_void_p]
 SIGNATURES['sgdfr_e4e_forward_f32'] = [_c_f32p, _i, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+_u8p = ctypes.c_void_p                   # uint8_t* on the device
+SIGNATURES['sgdfr_facecrop_boxes_f32'] = [_c_f32p, _i, _ip, _ip, ctypes.c_void_p]
+SIGNATURES['sgdfr_facecrop_forward_u8'] = [_u8p, _c_f32p, _i, _i, _i, _i, _i, _u8p, _ip, _c_f32p, _ip, _ip, _c_f32p, ctypes.c_void_p, _i64,
+                                           ctypes.c_void_p]
 E4E_PARAMS_256 = 423    # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
@@ -278,6 +282,8 @@ def load():
     for name in ('sgdfr_e4e_debug_elems', 'sgdfr_e4e_workspace_bytes'):
         getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int]
         getattr(lib, name).restype = ctypes.c_int64
+    lib.sgdfr_facecrop_workspace_bytes.argtypes = [ctypes.c_int] * 4
+    lib.sgdfr_facecrop_workspace_bytes.restype = ctypes.c_int64
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():

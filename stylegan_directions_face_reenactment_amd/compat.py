@@ -9,7 +9,8 @@ resolving to the reference checkout on sys.path.  ``install_lpips(state_dict)`` 
 ``libs.criteria.lpips.lpips`` so that unchanged ``LPIPS(net_type='alex')`` calls get it with those weights (no torchvision, no
 download); ``install_id_loss(path)`` (opt-in) mounts the HIP identity loss at ``libs.criteria.id_loss`` the same way.
 ``install_face_detector(state_dict)`` (opt-in) mounts the HIP S3FD detector at ``libs.face_models.sfd.sfd_detector`` so that an
-unchanged ``SFDDetector(device, path)`` (landmarks_estimation.py:118) gets it.  There is no ``install_landmarks``:
+unchanged ``SFDDetector(device, path)`` (landmarks_estimation.py:118) gets it.  ``install_face_crop()`` (opt-in) mounts the HIP
+alignment crop at ``libs.face_models.ffhq_cropping`` (numpy in, numpy out, as preprocess_image calls it).  There is no ``install_landmarks``:
 ``LandmarksEstimation`` crops and runs one face at a time around the FAN network; call ``face_detector.detect_landmarks`` or
 ``landmarks.get_landmarks`` instead.  ``libs.utilities.generic`` is NOT replaced wholesale
 (it also holds DECA glue); call ``patch_generic(module)`` to swap in the two fused functions.
@@ -153,3 +154,21 @@ def install_face_detector(state_dict=None):
     mod.__doc__ = 'HIP S3FD face detector mounted by stylegan_directions_face_reenactment_amd.compat.install_face_detector'
     _mount(FACE_DETECTOR_ALIAS, mod)
     return FACE_DETECTOR_ALIAS
+
+
+FACE_CROP_ALIAS = 'libs.face_models.ffhq_cropping'
+
+
+def install_face_crop():
+    """Mount a module at libs.face_models.ffhq_cropping whose crop_using_landmarks(image, landmarks) is the HIP alignment crop with
+    the reference's signature: a [H,W,3] uint8 array and [68,2] landmarks in, the [256,256,3] uint8 crop out, None where the
+    reference returns None (an empty box) and where the row is not valid (face_crop: a box beyond max(H, W) // 2 or a border wider
+    than the frame).  It copies to the GPU and back per call; a pipeline that stays on the device calls
+    reenact.preprocess_frames instead.  Parent packages that cannot be imported are created empty."""
+    from . import face_crop as hip_fc
+    _parent_packages(FACE_CROP_ALIAS)
+    mod = types.ModuleType(FACE_CROP_ALIAS)
+    mod.crop_using_landmarks = lambda image, landmarks: hip_fc.crop_image(image, landmarks)
+    mod.__doc__ = 'HIP alignment crop mounted by stylegan_directions_face_reenactment_amd.compat.install_face_crop'
+    _mount(FACE_CROP_ALIAS, mod)
+    return FACE_CROP_ALIAS

@@ -102,6 +102,23 @@ def invert_images(enc, G, images, truncation=1.0, trunc=None, as_uint8=False):
     return w, (images_to_uint8(frames) if as_uint8 else frames)
 
 
+@torch.no_grad()
+def preprocess_frames(det, fan, frames, out_size=256):
+    """The body of the reference's preprocess_image (libs/utilities/utils_inference.py:61-82) for a batch, without its
+    image_resize(width=1000): frames [B,H,W,3] uint8 on the device -> face_detector.detect_landmarks(rule='last_above_0.99',
+    input_range='255') on the float CHW view, as LandmarksEstimation.detect_landmarks is called there -> the alignment crop
+    (face_crop.crop_using_landmarks).  Returns (crops [B,S,S,3] uint8, x [B,3,S,S] float32 in [-1,1], ok [B] bool) with
+    ok = has_face & valid; x feeds `invert_images` directly.  One stream, no host synchronisation; rows with ok False hold nothing
+    of use."""
+    from . import face_crop
+    from .face_detector import detect_landmarks
+    face_crop._check_frames(frames)
+    images = frames.permute(0, 3, 1, 2).float()
+    pts, _, has_face = detect_landmarks(det, fan, images, rule='last_above_0.99', input_range='255')
+    (crops, x), valid = face_crop.crop_using_landmarks(frames, pts.contiguous(), out_size=out_size, as_tensor=True)
+    return crops, x, has_face & (valid != 0)
+
+
 def load_latent_codes(paths, device=None):
     """Read per-frame `.npy` codes back into one [B,n_latent,512] tensor (pinned staging, one H2D copy)."""
     codes = [np.load(p) for p in paths]
