@@ -13,12 +13,10 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "conv_tile.h"
 
 namespace sgdfr {
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlocks = 16;
 constexpr int kCrop = 224, kCropPlane = kCrop * kCrop;
@@ -26,7 +24,7 @@ constexpr int kStem = 112, kPool = 56;
 constexpr int kFeat = 2048, kHidden = 1024, kOut = 236;
 constexpr int kParams = 2 + 8 * kBlocks + 4;     // pointers sgdfr_deca_prepack_f32 takes
 constexpr int kMaxRows = 1024;
-constexpr int BM = 64, BN = 64, BK = 16, kThreads = 256;
+constexpr int BN = 64;
 // split K only below 512 output tiles, at most 512 / tiles slices: S * (output elements) <= 512 tiles
 constexpr int64_t kPartElems = 512LL * BM * BN;
 
@@ -60,7 +58,6 @@ struct PackLayout {
     BlockPack u[kBlocks];
     int64_t wf_fc1, wd_fc1, b_fc1, wf_fc2, wd_fc2, b_fc2, total;
 };
-static int64_t align64(int64_t v) { return (v + 63) & ~(int64_t)63; }
 static PackLayout pack_layout() {
     Block bs[kBlocks];
     make_blocks(bs);
@@ -147,15 +144,14 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, int b, int n, int p,
 
 template <int TAP, int KS, bool EXT>
 __global__ __launch_bounds__(kThreads) void deca_conv_kernel(ConvArgs a) {
-    __shared__ float xs[2][BK][BM + 4];    // pixels (MFMA B operand / columns)
-    __shared__ float ws[2][BK][BN + 4];    // output channels (MFMA A operand / rows)
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, split = blockIdx.z;
+    __shared__ ConvLds<BN> lds;
+    const int t = threadIdx.x, wv = t >> 6;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
     const int HWo = a.Ho * a.Wo, M = a.R * HWo;
     const int plane = a.Hs * a.Ws;
 
     // the pixel this thread gathers (fixed over K)
-    const int lm = t & (BM - 1), gm = m0 + lm;
+    const int gm = m0 + (t & (BM - 1));
     const bool mvalid = gm < M;
     int b = 0, oh = 0, ow = 0;
     if (mvalid) {
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void deca_conv_kernel(ConvArgs a) {
     const float* extb = EXT ? a.ext + (int64_t)b * (a.K - a.K1) * (a.He * a.We) : nullptr;
 
     const int nchunks = (a.K + BK - 1) / BK;
-    const int c0 = split * a.cps, c1 = min(nchunks, c0 + a.cps);
+    const int c0 = blockIdx.z * a.cps, c1 = min(nchunks, c0 + a.cps);
     float xr[4], wr[4];
     auto gload = [&](int c) {
         const int k0 = c * BK;
@@ -176,10 +172,10 @@ __global__ __launch_bounds__(kThreads) void deca_conv_kernel(ConvArgs a) {
         for (int i = 0; i < 4; ++i) {
             const int k = k0 + wv + 4 * i;
             float v = 0.f;
-            if (mvalid && k < a.K) {
+            if (k < a.K) {
                 if (EXT && k >= a.K1) {
                     const int sh = a.es - 1;   // es is 1 or 2
-                    if (!((oh | ow) & sh)) v = extb[((k - a.K1) * a.He + (oh >> sh)) * a.We + (ow >> sh)];
+                    if (mvalid && !((oh | ow) & sh)) v = extb[((k - a.K1) * a.He + (oh >> sh)) * a.We + (ow >> sh)];
                 } else {
                     const int ci = k / (KS * KS), r = k - ci * (KS * KS), kh = r / KS, kw = r - kh * KS;
                     int ih, iw;
@@ -196,92 +192,33 @@ __global__ __launch_bounds__(kThreads) void deca_conv_kernel(ConvArgs a) {
                         ih >>= 1, iw >>= 1;
                         ok = ok && ih < a.Hs && iw < a.Ws;
                     }
-                    if (ok) v = srcb[ci * plane + ih * a.Ws + iw];
+                    if (mvalid && ok) v = srcb[ci * plane + ih * a.Ws + iw];
                 }
             }
             xr[i] = v;
         }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = t + kThreads * i, n = e & (BN - 1), k = k0 + (e >> 6), gn = n0 + n;
-            wr[i] = (k < a.K && gn < a.N) ? a.wp[(int64_t)k * a.N + gn] : 0.f;
-        }
+        load_w<BN>(wr, a.wp, a.K, a.N, k0, n0);
     };
     auto sstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xs[buf][wv + 4 * i][lm] = xr[i];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = t + kThreads * i;
-            ws[buf][e >> 6][e & (BN - 1)] = wr[i];
-        }
+        store_x(lds.xs[buf], xr);
+        store_w<BN>(lds.ws[buf], wr);
     };
 
-    const int wm = wv & 1, wn = wv >> 1;
     floatx4 acc[2][2];
-    for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+    k_loop<BN>(lds, c0, c1, gload, sstore, acc);
 
-    if (c0 < c1) {
-        gload(c0);
-        sstore(0);
-    }
-    __syncthreads();
-    for (int c = c0; c < c1; ++c) {
-        const int buf = (c - c0) & 1;
-        const bool more = c + 1 < c1;
-        if (more) gload(c + 1);
-#pragma unroll
-        for (int ks = 0; ks < BK; ks += 4) {
-            const int kr = ks + (lane >> 4);
-            float wa[2], xa[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) wa[i] = ws[buf][kr][wn * 32 + i * 16 + (lane & 15)];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) xa[j] = xs[buf][kr][wm * 32 + j * 16 + (lane & 15)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], xa[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) sstore(buf ^ 1);   // the other buffer: every wave finished reading it before the previous barrier
-        __syncthreads();
-    }
-
-    // D[row = channel][col = pixel]: lane holds channel (lane>>4)*4 + r of a 16-row block, pixel lane&15
-    const bool raw = gridDim.z > 1;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int gp = m0 + wm * 32 + j * 16 + (lane & 15);
-        if (gp >= M) continue;
-        const int bb = gp / HWo, p = gp - bb * HWo;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gn = n0 + wn * 32 + i * 16 + (lane >> 4) * 4 + r;
-                if (gn >= a.N) continue;
-                const float v = acc[i][j][r];
-                if (raw)
-                    a.part[(int64_t)split * a.part_elems + ((int64_t)bb * a.N + gn) * HWo + p] = v;
-                else
-                    epilogue(a, bb, gn, p, v);
-            }
-    }
+    float* const slice = slice_of(a.part, a.part_elems);
+    for_each_output<BN>(acc, m0, n0, M, a.N, HWo, [=](int bb, int gn, int p, float v) {
+        if (slice)
+            slice[((int64_t)bb * a.N + gn) * HWo + p] = v;
+        else
+            epilogue(a, bb, gn, p, v);
+    });
 }
 
 // sum of the K slices in fixed order + the conv's epilogue
 __global__ __launch_bounds__(kThreads) void deca_finish_kernel(ConvArgs a, int S) {
-    const int HWo = a.Ho * a.Wo;
-    const int64_t n = a.part_elems, per_row = (int64_t)a.N * HWo;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-        float v = a.part[i];
-        for (int s = 1; s < S; ++s) v += a.part[(int64_t)s * n + i];
-        const int b = (int)(i / per_row);
-        const int64_t rem = i - b * per_row;
-        const int gn = (int)(rem / HWo), p = (int)(rem - (int64_t)gn * HWo);
-        epilogue(a, b, gn, p, v);
-    }
+    finish_slices(a.part, a.part_elems, S, a.N, a.Ho * a.Wo, [=](int b, int n, int p, float v) { epilogue(a, b, n, p, v); });
 }
 
 // ------------------------------------------------------------------ front: [-1,1] -> [0,255], affine bilinear crop, / 255
@@ -499,29 +436,11 @@ __global__ void deca_angles_kernel(const float* __restrict__ params, float* __re
 }
 
 // ------------------------------------------------------------------ host side
-int grid_1d(int64_t n) { return (int)std::min<int64_t>((n + kThreads - 1) / kThreads, 8192); }
-
-struct ConvPlan {
-    int S, cps, mt, nt;
-    int64_t out_elems;
-};
-// The number of K slices follows the output tiles, i.e. the layer and the row count, nothing else.
-static ConvPlan plan_conv(int R, int N, int Ho, int Wo, int K) {
-    ConvPlan p;
-    const int M = R * Ho * Wo;
-    p.mt = (M + BM - 1) / BM, p.nt = (N + BN - 1) / BN;
-    const int nchunks = (K + BK - 1) / BK, tiles = p.mt * p.nt;
-    int S = std::min(512 / std::max(tiles, 1), nchunks / 8);
-    S = std::max(1, std::min(S, 32));
-    p.cps = (nchunks + S - 1) / S;
-    p.S = (nchunks + p.cps - 1) / p.cps;
-    p.out_elems = (int64_t)M * N;
-    return p;
-}
-
 static int launch_conv(const ConvArgs& a0, int tap, int ks, bool ext, float* part, hipStream_t st) {
     ConvArgs a = a0;
-    const ConvPlan p = plan_conv(a.R, a.N, a.Ho, a.Wo, a.K);
+    // The number of K slices follows the output tiles, i.e. the layer and the row count, nothing else.
+    const int M = a.R * a.Ho * a.Wo;
+    const ConvPlan p = plan_conv(M, a.N, a.K, BN, conv_tiles(M, a.N, BN));
     SGDFR_REQUIRE(p.S == 1 || p.S * p.out_elems <= kPartElems, "deca: split-K partials of %lld floats exceed the workspace",
                   (long long)(p.S * p.out_elems));
     a.cps = p.cps;

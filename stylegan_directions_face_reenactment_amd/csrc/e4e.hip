@@ -21,18 +21,16 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "conv_tile.h"
 
 namespace sgdfr {
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kUnits = 24, kMaxHeads = 14, kMaxDepth = 6, kGroups = 3, kStyle = 512;
 constexpr int kMinRes = 32, kMaxRes = 256, kMaxRows = 256;
 constexpr int64_t kMaxPixels = 1LL << 24;           // rows * R * R: every element index of a 64-channel map stays below 2^31
 constexpr int kTrunkParams = 3 + 10 * kUnits + 4;   // stem, units, the two lateral convs
-constexpr int BM = 64, BN = 64, BK = 16, kThreads = 256;
+constexpr int BN = 64;
 // split K only below 192 output tiles, at most 512 / tiles slices: S * (output elements) <= 512 tiles of 64 x 64
 constexpr int kSplitBelow = 192;
 constexpr int64_t kPartElems = 512LL * BM * BN;
@@ -91,7 +89,6 @@ struct PackLayout {
     int64_t hw[kGroups][kMaxDepth], hb[kGroups][kMaxDepth];   // depth 0: [4608][G*512]; deeper: per head [4608][512]
     int64_t lw, lb, total;                                    // EqualLinear: per head [512][512] (scaled on the host), [512]
 };
-static int64_t align64(int64_t v) { return (v + 63) & ~(int64_t)63; }
 static PackLayout pack_layout(int R) {
     Unit us[kUnits];
     make_units(us, R);
@@ -190,16 +187,15 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, int b, int g, int n,
 
 template <int KS, int LOAD, bool SKIP>
 __global__ __launch_bounds__(kThreads) void e4e_conv_kernel(ConvArgs a) {
-    __shared__ float xs[2][BK][BM + 4];    // pixels (MFMA B operand / columns)
-    __shared__ float ws[2][BK][BN + 4];    // output channels (MFMA A operand / rows)
+    __shared__ ConvLds<BN> lds;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int g = blockIdx.y / a.ntg;
-    const int m0 = blockIdx.x * BM, n0 = (blockIdx.y - g * a.ntg) * BN, split = blockIdx.z;
+    const int m0 = blockIdx.x * BM, n0 = (blockIdx.y - g * a.ntg) * BN;
     const int HWo = a.Ho * a.Wo, M = a.R * HWo;
     const int plane = a.Hs * a.Ws;
 
     // the pixel this thread gathers (fixed over K)
-    const int lm = t & (BM - 1), gm = m0 + lm;
+    const int gm = m0 + (t & (BM - 1));
     const bool mvalid = gm < M;
     int b = 0, oh = 0, ow = 0;
     if (mvalid) {
@@ -212,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void e4e_conv_kernel(ConvArgs a) {
     const float* wg = a.wp + g * a.w_gs;
 
     const int nchunks = (a.K + BK - 1) / BK;
-    const int c0 = split * a.cps, c1 = min(nchunks, c0 + a.cps);
+    const int c0 = blockIdx.z * a.cps, c1 = min(nchunks, c0 + a.cps);
     float xr[4], wr[4];
     auto gload = [&](int c) {
         const int k0 = c * BK;
@@ -243,77 +239,30 @@ __global__ __launch_bounds__(kThreads) void e4e_conv_kernel(ConvArgs a) {
         }
     };
     auto sstore = [&](int buf) {
+        store_x(lds.xs[buf], xr);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) xs[buf][wv + 4 * i][lm] = xr[i], ws[buf][wv + 4 * i][lane] = wr[i];
+        for (int i = 0; i < 4; ++i) lds.ws[buf][wv + 4 * i][lane] = wr[i];
     };
 
-    const int wm = wv & 1, wn = wv >> 1;
     floatx4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+    k_loop<BN>(lds, c0, c1, gload, sstore, acc);
 
-    if (c0 < c1) {
-        gload(c0);
-        sstore(0);
-    }
-    __syncthreads();
-    for (int c = c0; c < c1; ++c) {
-        const int buf = (c - c0) & 1;
-        const bool more = c + 1 < c1;
-        if (more) gload(c + 1);
-#pragma unroll
-        for (int ks = 0; ks < BK; ks += 4) {
-            const int kr = ks + (lane >> 4);
-            float wa[2], xa[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) wa[i] = ws[buf][kr][wn * 32 + i * 16 + (lane & 15)];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) xa[j] = xs[buf][kr][wm * 32 + j * 16 + (lane & 15)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], xa[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) sstore(buf ^ 1);   // the other buffer: every wave finished reading it before the previous barrier
-        __syncthreads();
-    }
-
-    // D[row = channel][col = pixel]: lane holds channel (lane>>4)*4 + r of a 16-row block, pixel lane&15
-    const bool sliced = gridDim.z > 1;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int gp = m0 + wm * 32 + j * 16 + (lane & 15);
-        if (gp >= M) continue;
-        const int bb = gp / HWo, p = gp - bb * HWo;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gn = n0 + wn * 32 + i * 16 + (lane >> 4) * 4 + r;
-                if (gn >= a.N) continue;
-                const float v = acc[i][j][r];
-                if (sliced)
-                    a.part[(int64_t)split * a.part_elems + (((int64_t)bb * a.G + g) * a.N + gn) * HWo + p] = v;
-                else
-                    epilogue(a, bb, g, gn, p, v);
-            }
-    }
+    // the partials are [R * G, N, HWo]: (row, group) is the walk's row
+    float* const slice = slice_of(a.part, a.part_elems);
+    for_each_output<BN>(acc, m0, n0, M, a.N, HWo, [=](int bb, int gn, int p, float v) {
+        if (slice)
+            slice[(((int64_t)bb * a.G + g) * a.N + gn) * HWo + p] = v;
+        else
+            epilogue(a, bb, g, gn, p, v);
+    });
 }
 
 // sum of the K slices in fixed order + the conv's epilogue
 __global__ __launch_bounds__(kThreads) void e4e_finish_kernel(ConvArgs a, int S) {
-    const int HWo = a.Ho * a.Wo;
-    const int64_t n = a.part_elems, per_group = (int64_t)a.N * HWo;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-        float v = a.part[i];
-        for (int s = 1; s < S; ++s) v += a.part[(int64_t)s * n + i];
-        const int bg = (int)(i / per_group), b = bg / a.G, g = bg - b * a.G;
-        const int64_t rem = i - bg * per_group;
-        const int gn = (int)(rem / HWo), p = (int)(rem - (int64_t)gn * HWo);
-        epilogue(a, b, g, gn, p, v);
-    }
+    finish_slices(a.part, a.part_elems, S, a.N, a.Ho * a.Wo, [=](int bg, int n, int p, float v) {
+        const int b = bg / a.G;
+        epilogue(a, b, bg - b * a.G, n, p, v);
+    });
 }
 
 // ------------------------------------------------------------------ SE gate
@@ -376,35 +325,18 @@ __global__ __launch_bounds__(kThreads) void e4e_wplus_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------ host side
-int grid_1d(int64_t n) { return (int)std::min<int64_t>((n + kThreads - 1) / kThreads, 8192); }
-
-struct ConvPlan {
-    int S, cps, mt, nt;
-    int64_t out_elems;
-};
-static ConvPlan plan_conv(int R, int G, int N, int Ho, int Wo, int K) {
-    ConvPlan p;
-    const int M = R * Ho * Wo;
-    p.mt = (M + BM - 1) / BM, p.nt = (N + BN - 1) / BN;
-    const int nchunks = (K + BK - 1) / BK, tiles = p.mt * p.nt * G;
-    // a grid that already puts a block on three quarters of the 256 CUs runs whole: a second block per CU does not pay for the
-    // pass over the partials.  Below that, up to 512 / tiles slices of at least 8 chunks.
-    int S = tiles >= kSplitBelow ? 1 : std::min(512 / std::max(tiles, 1), nchunks / 8);
-    S = std::max(1, std::min(S, 32));
-    p.cps = (nchunks + S - 1) / S;
-    p.S = (nchunks + p.cps - 1) / p.cps;
-    p.out_elems = (int64_t)M * N * G;
-    return p;
-}
-
 static int launch_conv(const ConvArgs& a0, int ks, int load, bool skip, float* part, hipStream_t st) {
     ConvArgs a = a0;
-    const ConvPlan p = plan_conv(a.R, a.G, a.N, a.Ho, a.Wo, a.K);
-    SGDFR_REQUIRE(p.S == 1 || p.S * p.out_elems <= kPartElems, "e4e: split-K partials of %lld floats exceed the workspace",
-                  (long long)(p.S * p.out_elems));
+    // the plan looks at the tiles of all groups.  A grid that already puts a block on three quarters of the 256 CUs runs whole: a
+    // second block per CU does not pay for the pass over the partials.  Below that, up to 512 / tiles slices of at least 8 chunks.
+    const int M = a.R * a.Ho * a.Wo, tiles = conv_tiles(M, a.N, BN) * a.G;
+    const ConvPlan p = plan_conv(M, a.N, a.K, BN, tiles, tiles >= kSplitBelow);
+    const int64_t out_elems = p.out_elems * a.G;
+    SGDFR_REQUIRE(p.S == 1 || p.S * out_elems <= kPartElems, "e4e: split-K partials of %lld floats exceed the workspace",
+                  (long long)(p.S * out_elems));
     a.cps = p.cps, a.ntg = p.nt;
     a.part = part;
-    a.part_elems = p.out_elems;
+    a.part_elems = out_elems;
     const dim3 grid(p.mt, p.nt * a.G, p.S);
     bool done = false;
 #define SGDFR_E4E_CONV(KS_, LD_, SKIP_)                                                        \
@@ -421,7 +353,7 @@ static int launch_conv(const ConvArgs& a0, int ks, int load, bool skip, float* p
     SGDFR_REQUIRE(done, "e4e: no conv instance for k=%d load=%d skip=%d", ks, load, (int)skip);
     if (check_launch("e4e conv")) return 2;
     if (p.S > 1) {
-        hipLaunchKernelGGL(e4e_finish_kernel, dim3(grid_1d(p.out_elems)), dim3(kThreads), 0, st, a, p.S);
+        hipLaunchKernelGGL(e4e_finish_kernel, dim3(grid_1d(out_elems)), dim3(kThreads), 0, st, a, p.S);
         if (check_launch("e4e finish")) return 2;
     }
     return 0;

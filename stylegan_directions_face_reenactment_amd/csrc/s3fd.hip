@@ -21,20 +21,17 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "conv_tile.h"
 
 namespace sgdfr {
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTrunk = 19, kLevels = 6;
 constexpr int kParams = 2 * (kTrunk + kLevels);
 constexpr int kMaxRows = 256, kMaxSide = 4096, kMinSide = 32, kMaxCapacity = 16384;
 constexpr int64_t kMaxPixels = 1LL << 24;           // rows * H * W: every element index of a 64-channel map stays below 2^31
-constexpr int BM = 64, BK = 16, kThreads = 256;
 // split K only below 512 output tiles, at most 512 / tiles slices: S * (output elements) <= 512 tiles of 64 x 64
-constexpr int64_t kPartElems = 512LL * 64 * 64;
+constexpr int64_t kPartElems = 512LL * BM * 64;
 
 // ------------------------------------------------------------------ network geometry
 struct Layer {
@@ -81,7 +78,6 @@ static bool size_ok(int rows, int H, int W) {
 struct PackLayout {
     int64_t w[kTrunk], b[kTrunk], hw[kLevels], hb[kLevels], total;
 };
-static int64_t align64(int64_t v) { return (v + 63) & ~(int64_t)63; }
 static PackLayout pack_layout() {
     PackLayout p;
     int64_t o = 0;
@@ -131,22 +127,17 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, int b, int n, int p,
     a.out[((int64_t)b * a.N + n) * (a.Ho * a.Wo) + p] = v;
 }
 
-// BN = 64: the trunk's tile, waves as 2 (pixels) x 2 (channels), 2 x 2 MFMA blocks each.  BN = 16: the heads', waves as 4 x 1, one block each.
+// BN = 64: the trunk's tile.  BN = 16: the heads' (conv_tile.h Tile<BN>).
 template <int KS, int BN>
 __global__ __launch_bounds__(kThreads) void s3fd_conv_kernel(ConvArgs a) {
-    constexpr int WN = BN == 64 ? 2 : 1, WM = 4 / WN;      // waves along channels / pixels
-    constexpr int TM = BM / (16 * WM), TN = BN / (16 * WN);   // 16-wide blocks per wave
-    constexpr int WL = BK * BN / kThreads;                  // filter values a thread stages per chunk
-    static_assert(BN == 64 || BN == 16, "two tiles");
-    __shared__ float xs[2][BK][BM + 4];    // pixels (MFMA B operand / columns)
-    __shared__ float ws[2][BK][BN + 4];    // output channels (MFMA A operand / rows)
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, split = blockIdx.z;
+    __shared__ ConvLds<BN> lds;
+    const int t = threadIdx.x, wv = t >> 6;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
     const int HWo = a.Ho * a.Wo, M = a.R * HWo;
     const int plane = a.Hs * a.Ws;
 
     // the pixel this thread gathers (fixed over K)
-    const int lm = t & (BM - 1), gm = m0 + lm;
+    const int gm = m0 + (t & (BM - 1));
     const bool mvalid = gm < M;
     int b = 0, oh = 0, ow = 0;
     if (mvalid) {
@@ -159,8 +150,8 @@ __global__ __launch_bounds__(kThreads) void s3fd_conv_kernel(ConvArgs a) {
     const float* rnb = a.rn ? a.rn + (int64_t)b * plane : nullptr;
 
     const int nchunks = (a.K + BK - 1) / BK;
-    const int c0 = split * a.cps, c1 = min(nchunks, c0 + a.cps);
-    float xr[4], wr[WL];
+    const int c0 = blockIdx.z * a.cps, c1 = min(nchunks, c0 + a.cps);
+    float xr[4], wr[Tile<BN>::WL];
     auto gload = [&](int c) {
         const int k0 = c * BK;
 #pragma unroll
@@ -178,89 +169,28 @@ __global__ __launch_bounds__(kThreads) void s3fd_conv_kernel(ConvArgs a) {
             }
             xr[i] = v;
         }
-#pragma unroll
-        for (int i = 0; i < WL; ++i) {
-            const int e = t + kThreads * i, n = e & (BN - 1), k = k0 + e / BN, gn = n0 + n;
-            wr[i] = (k < a.K && gn < a.N) ? a.wp[(int64_t)k * a.N + gn] : 0.f;
-        }
+        load_w<BN>(wr, a.wp, a.K, a.N, k0, n0);
     };
     auto sstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xs[buf][wv + 4 * i][lm] = xr[i];
-#pragma unroll
-        for (int i = 0; i < WL; ++i) {
-            const int e = t + kThreads * i;
-            ws[buf][e / BN][e & (BN - 1)] = wr[i];
-        }
+        store_x(lds.xs[buf], xr);
+        store_w<BN>(lds.ws[buf], wr);
     };
 
-    const int wm = wv % WM, wn = wv / WM;
-    floatx4 acc[TN][TM];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+    floatx4 acc[Tile<BN>::TN][Tile<BN>::TM];
+    k_loop<BN>(lds, c0, c1, gload, sstore, acc);
 
-    if (c0 < c1) {
-        gload(c0);
-        sstore(0);
-    }
-    __syncthreads();
-    for (int c = c0; c < c1; ++c) {
-        const int buf = (c - c0) & 1;
-        const bool more = c + 1 < c1;
-        if (more) gload(c + 1);
-#pragma unroll
-        for (int ks = 0; ks < BK; ks += 4) {
-            const int kr = ks + (lane >> 4);
-            float wa[TN], xa[TM];
-#pragma unroll
-            for (int i = 0; i < TN; ++i) wa[i] = ws[buf][kr][wn * (16 * TN) + i * 16 + (lane & 15)];
-#pragma unroll
-            for (int j = 0; j < TM; ++j) xa[j] = xs[buf][kr][wm * (16 * TM) + j * 16 + (lane & 15)];
-#pragma unroll
-            for (int i = 0; i < TN; ++i)
-#pragma unroll
-                for (int j = 0; j < TM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], xa[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) sstore(buf ^ 1);   // the other buffer: every wave finished reading it before the previous barrier
-        __syncthreads();
-    }
-
-    // D[row = channel][col = pixel]: lane holds channel (lane>>4)*4 + r of a 16-row block, pixel lane&15
-    const bool sliced = gridDim.z > 1;
-#pragma unroll
-    for (int j = 0; j < TM; ++j) {
-        const int gp = m0 + wm * (16 * TM) + j * 16 + (lane & 15);
-        if (gp >= M) continue;
-        const int bb = gp / HWo, p = gp - bb * HWo;
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gn = n0 + wn * (16 * TN) + i * 16 + (lane >> 4) * 4 + r;
-                if (gn >= a.N) continue;
-                const float v = acc[i][j][r];
-                if (sliced)
-                    a.part[(int64_t)split * a.part_elems + ((int64_t)bb * a.N + gn) * HWo + p] = v;
-                else
-                    epilogue(a, bb, gn, p, v);
-            }
-    }
+    float* const slice = slice_of(a.part, a.part_elems);
+    for_each_output<BN>(acc, m0, n0, M, a.N, HWo, [=](int bb, int gn, int p, float v) {
+        if (slice)
+            slice[((int64_t)bb * a.N + gn) * HWo + p] = v;
+        else
+            epilogue(a, bb, gn, p, v);
+    });
 }
 
 // sum of the K slices in fixed order + the conv's epilogue
 __global__ __launch_bounds__(kThreads) void s3fd_finish_kernel(ConvArgs a, int S) {
-    const int HWo = a.Ho * a.Wo;
-    const int64_t n = a.part_elems, per_row = (int64_t)a.N * HWo;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-        float v = a.part[i];
-        for (int s = 1; s < S; ++s) v += a.part[(int64_t)s * n + i];
-        const int b = (int)(i / per_row);
-        const int64_t rem = i - b * per_row;
-        const int gn = (int)(rem / HWo), p = (int)(rem - (int64_t)gn * HWo);
-        epilogue(a, b, gn, p, v);
-    }
+    finish_slices(a.part, a.part_elems, S, a.N, a.Ho * a.Wo, [=](int b, int n, int p, float v) { epilogue(a, b, n, p, v); });
 }
 
 // ------------------------------------------------------------------ max_pool2d(2, 2), floor: [planes, hi, wi] -> [planes, hi/2, wi/2]
@@ -492,29 +422,11 @@ __global__ __launch_bounds__(kThreads) void s3fd_nms_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------ host side
-int grid_1d(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + kThreads - 1) / kThreads, 1), 8192); }
-
-struct ConvPlan {
-    int S, cps, mt, nt;
-    int64_t out_elems;
-};
-// The number of K slices follows the output tiles, i.e. the layer, the image size and the row count, nothing else.
-static ConvPlan plan_conv(int R, int N, int Ho, int Wo, int K, int bn) {
-    ConvPlan p;
-    const int M = R * Ho * Wo;
-    p.mt = (M + BM - 1) / BM, p.nt = (N + bn - 1) / bn;
-    const int nchunks = (K + BK - 1) / BK, tiles = p.mt * p.nt;
-    int S = std::min(512 / std::max(tiles, 1), nchunks / 8);
-    S = std::max(1, std::min(S, 32));
-    p.cps = (nchunks + S - 1) / S;
-    p.S = (nchunks + p.cps - 1) / p.cps;
-    p.out_elems = (int64_t)M * N;
-    return p;
-}
-
 static int launch_conv(const ConvArgs& a0, int ks, bool head, float* part, hipStream_t st) {
     ConvArgs a = a0;
-    const ConvPlan p = plan_conv(a.R, a.N, a.Ho, a.Wo, a.K, head ? 16 : 64);
+    // The number of K slices follows the output tiles, i.e. the layer, the image size and the row count, nothing else.
+    const int M = a.R * a.Ho * a.Wo, bn = head ? 16 : 64;
+    const ConvPlan p = plan_conv(M, a.N, a.K, bn, conv_tiles(M, a.N, bn));
     SGDFR_REQUIRE(p.S == 1 || p.S * p.out_elems <= kPartElems, "s3fd: split-K partials of %lld floats exceed the workspace",
                   (long long)(p.S * p.out_elems));
     a.cps = p.cps;
