@@ -72,14 +72,22 @@ def median(img, dtype=np.float32):
     return ((flat[n // 2 - 1] + flat[n // 2]) / dtype(2)).astype(dtype)
 
 
-def padded_frame(frame, box, dtype=np.float32):
-    """pad_img_to_fit_bbox: the whole padded frame after both blends, and the box moved into it."""
+def first_blend(frame, box, dtype=np.float32):
+    """pad_img_to_fit_bbox up to its median: the padded frame after the Gaussian blend (what np.median sees), and the mask."""
     H, W, _ = frame.shape
     pl, pt, pr, pb = borders(box, H, W)
     img = np.pad(frame, ((pt, pb), (pl, pr), (0, 0)), mode='symmetric').astype(dtype)
     h, w, _ = img.shape
     mask = feather_mask(h, w, (pl, pt, pr, pb), dtype)
     img = img + (gaussian(img, dtype) - img) * np.clip(mask * dtype(3.0) + dtype(1.0), dtype(0.0), dtype(1.0))
+    return img, mask
+
+
+def padded_frame(frame, box, dtype=np.float32):
+    """pad_img_to_fit_bbox: the whole padded frame after both blends, and the box moved into it."""
+    H, W, _ = frame.shape
+    pl, pt, pr, pb = borders(box, H, W)
+    img, mask = first_blend(frame, box, dtype)
     img = img + (median(img, dtype) - img) * np.clip(mask, dtype(0.0), dtype(1.0))
     x1, y1, x2, y2 = box
     return img, (x1 + pl, y1 + pt, x2 + pl, y2 + pt)
