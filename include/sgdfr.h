@@ -29,6 +29,9 @@
  *   sgdfr_torgb_fwd_f32        model.py:350-359 ToRGB.forward (1x1 modconv, bias, Upsample(skip) :38-46, add)
  *   sgdfr_make_shift_f32       run_inference.py:201-254 Inference.make_shift, libs/utilities/utils_train.py:127-175 make_shift_vector
  *   sgdfr_make_shift_random_f32 libs/utilities/utils_train.py:227-286 (single-direction half of make_shift_vector_50)
+ *   sgdfr_gt_reenacted_f32     libs/utilities/utils_train.py:291-374 get_params_gt_reenacted (per-row host loop with one
+ *                              device->host read of target_indices there; one launch here), with batch_euler2axis of
+ *                              libs/DECA/decalib/utils/rotation_converter.py:306-307
  */
 #ifndef SGDFR_H
 #define SGDFR_H
@@ -428,6 +431,24 @@ int sgdfr_make_shift_f32(const float* ang_s, int64_t ang_s_bstride, const float*
 int sgdfr_make_shift_random_f32(const float* ang_s, const float* pose_s, const float* exp_s, int pose_dim, int exp_dim,
                                 const int* which, const float* u, float shift_scale, const struct sgdfr_direction* table,
                                 int D, float* shift, int N, void* stream);
+
+/* Ground-truth coefficients of the `disentanglement_50` training step (libs/utilities/utils_train.py:291-374
+ * get_params_gt_reenacted) for the whole batch in one launch, one thread per row; B must be even.
+ *   rows <  B/2: pose_gt / exp_gt = the target's pose / alpha_exp;
+ *   rows >= B/2: the source's, then table[which[row - B/2]] (device int32 [B/2], the indices make_shift_vector_50 drew) moves
+ *     one coefficient by shift[row, which] (shift [B,D], the vector make_shift_vector_50 returned):
+ *     SGDFR_DIR_ANGLE col c: start = angle[c] * shift_scale / b, angle[c] <- (start + shift) * b / shift_scale (b = angle_scales[c]),
+ *       the three angles (degrees) -> radians -> euler_to_quaternion -> quaternion_to_angle_axis (rotation_converter.py:48-90,
+ *       256-303, both `where` branches), then pose[0] = aa[1], pose[1] = -aa[0], pose[2] = aa[2] (the reference's swap);
+ *     SGDFR_DIR_JAW / SGDFR_DIR_EXP col c: x <- ((a * x + b + shift) - b) / a on pose[c] / alpha_exp[c];
+ *     SGDFR_DIR_ZERO, or an index outside 0..D-1: the row stays the source's (the reference's ifs fall through).
+ * float32 arithmetic as sgdfr_make_shift_f32's arith 1: one rounding per operation, no fma, true division.  Against the
+ * reference on CPU tensors: bit-identical except the three rotated pose entries, which carry the device library's sinf /
+ * cosf / atan2f.  All arrays contiguous: pose [B,pose_dim] (pose_dim >= 3), alpha_exp [B,exp_dim], angles [B,3]; the outputs
+ * must not overlap the inputs. */
+int sgdfr_gt_reenacted_f32(const float* pose_s, const float* exp_s, const float* ang_s, const float* pose_t, const float* exp_t,
+                           int pose_dim, int exp_dim, const float* shift, const int* which, float shift_scale,
+                           const struct sgdfr_direction* table, int D, float* pose_gt, float* exp_gt, int B, void* stream);
 
 /* ---- backward helpers (autograd of model.py:232-359 as restated in SURVEY.md Appendix C) ------------------------ */
 

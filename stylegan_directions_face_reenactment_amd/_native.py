@@ -101,6 +101,8 @@ SIGNATURES['sgdfr_make_shift_f32'] = [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _i6
                                       ctypes.POINTER(Direction), _i, _c_f32p, _i, _i, ctypes.c_void_p]
 SIGNATURES['sgdfr_make_shift_random_f32'] = [_c_f32p, _c_f32p, _c_f32p, _i, _i, ctypes.c_void_p, _c_f32p, _f,
                                              ctypes.POINTER(Direction), _i, _c_f32p, _i, ctypes.c_void_p]
+SIGNATURES['sgdfr_gt_reenacted_f32'] = [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i, _i, _c_f32p, ctypes.c_void_p, _f,
+                                        ctypes.POINTER(Direction), _i, _c_f32p, _c_f32p, _i, ctypes.c_void_p]
 
 
 class StyleLayer(ctypes.Structure):

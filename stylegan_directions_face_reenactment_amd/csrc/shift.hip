@@ -81,6 +81,74 @@ __global__ __launch_bounds__(256) void make_shift_random_kernel(ShiftSrc src, Di
     out[i] = v;
 }
 
+// batch_euler2axis(deg2rad(angles)) (decalib/utils/rotation_converter.py:48-90, 256-307) for one row, every float32 operation
+// of the tensor code rounded on its own and in its order: x*pi/180, the half angles, euler_to_quaternion's products,
+// quaternion_to_angle_axis with both of its `where`s (cos_theta < 0; sin^2 > 0, else k = 2).  sinf / cosf / atan2f are the device
+// library's: an ulp or two from the host's, which is all that separates this from the reference's own fp32 result.
+__device__ __forceinline__ void euler_deg_to_axis(const float ang[3], float aa[3]) {
+    const float pi = 3.14159265358979323846f;
+    float c[3], s[3];
+    for (int i = 0; i < 3; ++i) {
+        const float h = __fdiv_rn(__fdiv_rn(__fmul_rn(ang[i], pi), 180.f), 2.f);
+        c[i] = cosf(h);
+        s[i] = sinf(h);
+    }
+    const float cx = c[0], cy = c[1], cz = c[2], sx = s[0], sy = s[1], sz = s[2];
+    const float q0 = __fsub_rn(__fmul_rn(__fmul_rn(cx, cy), cz), __fmul_rn(__fmul_rn(sx, sy), sz));
+    const float q1 = __fadd_rn(__fmul_rn(__fmul_rn(cx, sy), sz), __fmul_rn(__fmul_rn(cy, cz), sx));
+    const float q2 = __fsub_rn(__fmul_rn(__fmul_rn(cx, cz), sy), __fmul_rn(__fmul_rn(sx, cy), sz));
+    const float q3 = __fadd_rn(__fmul_rn(__fmul_rn(cx, cy), sz), __fmul_rn(__fmul_rn(sx, cz), sy));
+    const float sin2 = __fadd_rn(__fadd_rn(__fmul_rn(q1, q1), __fmul_rn(q2, q2)), __fmul_rn(q3, q3));
+    const float sin_t = __fsqrt_rn(sin2);
+    const float two_t = __fmul_rn(2.f, q0 < 0.f ? atan2f(-sin_t, -q0) : atan2f(sin_t, q0));
+    const float k = sin2 > 0.f ? __fdiv_rn(two_t, sin_t) : 2.f;
+    aa[0] = __fmul_rn(q1, k);
+    aa[1] = __fmul_rn(q2, k);
+    aa[2] = __fmul_rn(q3, k);
+}
+
+// get_params_gt_reenacted (utils_train.py:291-374), one thread per row: the first half of the batch copies the target's pose and
+// expression, a row of the second half copies the source's and moves the ONE coefficient its drawn direction which[row - B/2]
+// drives by the drawn shift.  An index outside the table, or one the table does not drive, leaves the source copy (the
+// reference's chain of ifs falls through in the same way).
+__global__ __launch_bounds__(64) void gt_reenacted_kernel(ShiftSrc src, const float* __restrict__ pose_t, const float* __restrict__ exp_t,
+                                                          const float* __restrict__ shift, const int* __restrict__ which, DirTable tab,
+                                                          int D, float shift_scale, float* __restrict__ pose_gt,
+                                                          float* __restrict__ exp_gt, int B, int pose_dim, int exp_dim) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= B) return;
+    const int half = B / 2;
+    const bool first = n < half;
+    const float* pose = (first ? pose_t : src.base[1]) + (int64_t)n * pose_dim;
+    const float* expr = (first ? exp_t : src.base[2]) + (int64_t)n * exp_dim;
+    float* po = pose_gt + (int64_t)n * pose_dim;
+    float* eo = exp_gt + (int64_t)n * exp_dim;
+    for (int j = 0; j < pose_dim; ++j) po[j] = pose[j];
+    for (int j = 0; j < exp_dim; ++j) eo[j] = expr[j];
+    if (first) return;
+    const int ind = which[n - half];
+    if (ind < 0 || ind >= D) return;
+    const sgdfr_direction e = tab.d[ind];
+    const float sh = shift[(int64_t)n * D + ind];
+    if (e.kind == SGDFR_DIR_ANGLE) {
+        const float* a = src.base[0] + (int64_t)n * 3;
+        float ang[3] = {a[0], a[1], a[2]}, aa[3];
+        const float start = __fdiv_rn(__fmul_rn(e.col == 0 ? ang[0] : (e.col == 1 ? ang[1] : ang[2]), shift_scale), (float)e.b);
+        const float moved = __fdiv_rn(__fmul_rn(__fadd_rn(start, sh), (float)e.b), shift_scale);
+        for (int j = 0; j < 3; ++j) ang[j] = j == e.col ? moved : ang[j];     // (a select: no dynamically indexed private array)
+        euler_deg_to_axis(ang, aa);
+        po[0] = aa[1];                                                          // utils_train.py:311-314: the reference's swap
+        po[1] = -aa[0];
+        po[2] = aa[2];
+    } else if (e.kind == SGDFR_DIR_JAW || e.kind == SGDFR_DIR_EXP) {
+        const float fa = (float)e.a, fb = (float)e.b;
+        const float x = e.kind == SGDFR_DIR_JAW ? pose[e.col] : expr[e.col];
+        const float moved = __fdiv_rn(__fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(fa, x), fb), sh), fb), fa);
+        if (e.kind == SGDFR_DIR_JAW) po[e.col] = moved;
+        else eo[e.col] = moved;
+    }
+}
+
 static int check_table(const sgdfr_direction* table, int D, int pose_dim, int exp_dim, DirTable* out) {
     SGDFR_REQUIRE(table && D >= 1 && D <= SGDFR_MAX_DIRECTIONS, "make_shift: 1..%d directions, got %d", SGDFR_MAX_DIRECTIONS, D);
     for (int k = 0; k < D; ++k) {
@@ -129,4 +197,23 @@ extern "C" int sgdfr_make_shift_random_f32(const float* ang_s, const float* pose
     hipLaunchKernelGGL(make_shift_random_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), src, tab, D, which, u,
                        shift_scale, shift, N);
     return check_launch("make_shift_random");
+}
+
+extern "C" int sgdfr_gt_reenacted_f32(const float* pose_s, const float* exp_s, const float* ang_s, const float* pose_t, const float* exp_t,
+                                      int pose_dim, int exp_dim, const float* shift, const int* which, float shift_scale,
+                                      const struct sgdfr_direction* table, int D, float* pose_gt, float* exp_gt, int B, void* stream) {
+    SGDFR_REQUIRE(B >= 0 && B % 2 == 0, "gt_reenacted: the batch must be even (two halves), got %d", B);
+    SGDFR_REQUIRE(pose_dim >= 3 && exp_dim >= 1, "gt_reenacted: bad sizes pose_dim=%d exp_dim=%d", pose_dim, exp_dim);
+    SGDFR_REQUIRE(shift_scale != 0.f, "gt_reenacted: shift_scale is zero");
+    DirTable tab;
+    if (int rc = check_table(table, D, pose_dim, exp_dim, &tab)) return rc;
+    for (int k = 0; k < D; ++k)
+        SGDFR_REQUIRE((tab.d[k].kind != SGDFR_DIR_JAW && tab.d[k].kind != SGDFR_DIR_EXP) || tab.d[k].a != 0.0,
+                      "gt_reenacted: direction %d has a zero slope", k);
+    if (B == 0) return 0;
+    SGDFR_REQUIRE(pose_s && exp_s && ang_s && pose_t && exp_t && shift && which && pose_gt && exp_gt, "gt_reenacted: null pointer");
+    ShiftSrc src{{ang_s, pose_s, exp_s}, {3, pose_dim, exp_dim}};
+    hipLaunchKernelGGL(gt_reenacted_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), src, pose_t, exp_t, shift, which, tab, D,
+                       shift_scale, pose_gt, exp_gt, B, pose_dim, exp_dim);
+    return check_launch("gt_reenacted");
 }

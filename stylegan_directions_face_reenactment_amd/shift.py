@@ -5,6 +5,7 @@ Counterparts, same names and argument order:
   * ``ShiftVectors.make_shift``          run_inference.py:201-254   (Inference.make_shift; per frame, ~10 host syncs there)
   * ``ShiftVectors.make_shift_vector``   libs/utilities/utils_train.py:127-175
   * ``ShiftVectors.make_shift_vector_50``libs/utilities/utils_train.py:177-288
+  * ``ShiftVectors.get_params_gt_reenacted`` libs/utilities/utils_train.py:291-374 (one launch; a per-row host loop there)
 
 The reference pulls every 3DMM parameter to the host (``.detach().cpu().numpy()``), does scalar arithmetic there and
 uploads the 15 numbers again -- once per target frame.  Here ``params_*`` / ``angles_*`` stay device tensors for the whole
@@ -183,3 +184,38 @@ class ShiftVectors:
         N.call('sgdfr_make_shift_random_f32', N.ptr(a2), N.ptr(p2), N.ptr(e2), p2.shape[1], e2.shape[1],
                N.ptr(which), N.ptr(u), float(self.shift_scale), self._table_train, D, N.ptr(out[h:]), h, N.stream())
         return out, (which.cpu().numpy() if indices_on_host else which)
+
+    def get_params_gt_reenacted(self, param_source, param_target, shift_vector, target_indices, angles_source):
+        """utils_train.py:291-374: the ground-truth coefficients {'pose' [B,6], 'exp' [B,50]} of the `disentanglement_50`
+        step, for `shift_vector`, `target_indices` as make_shift_vector_50 returned them.  Rows below B/2 take the target's
+        pose and expression; a row of the second half takes the source's with the one coefficient its drawn direction drives
+        moved by the drawn shift (a pose angle goes through batch_euler2axis and the reference's component swap).  One launch,
+        no synchronisation: the reference loops over the rows on the host and reads int(target_indices[count]).  The source
+        and target dicts are not modified; nothing here is differentiable (the result is a target)."""
+        rows = lambda v: int(v.shape[0]) if hasattr(v, 'shape') else len(v)
+        B = rows(angles_source)
+        if B % 2 != 0:
+            raise RuntimeError('Batch size should be even number!')          # utils_train.py:179-181 (print + exit there)
+        h, D = B // 2, self.learned_directions
+        if rows(target_indices) != h or getattr(target_indices, 'ndim', 1) != 1:
+            raise RuntimeError('get_params_gt_reenacted: need %d target_indices for a batch of %d' % (h, B))
+        ang = _dev(angles_source)
+        ps, es = _dev(param_source['pose'], ang), _dev(param_source['alpha_exp'], ang)
+        pt, et = _dev(param_target['pose'], ang), _dev(param_target['alpha_exp'], ang)
+        sv = _dev(shift_vector, ang)
+        if not isinstance(target_indices, torch.Tensor):
+            target_indices = torch.as_tensor(np.asarray(target_indices), dtype=torch.int32)
+        which = target_indices.detach().to(device=ang.device, dtype=torch.int32).contiguous()
+        if ang.ndim != 2 or ang.shape[1] != 3:
+            raise RuntimeError('get_params_gt_reenacted: angles must be [B,3] (yaw, pitch, roll), got %s' % (tuple(ang.shape),))
+        for name, s, t in (('pose', ps, pt), ('alpha_exp', es, et)):
+            if s.ndim != 2 or s.shape[0] != B or tuple(t.shape) != tuple(s.shape):
+                raise RuntimeError('get_params_gt_reenacted: source %s %s / target %s do not describe %d rows'
+                                   % (name, tuple(s.shape), tuple(t.shape), B))
+        if tuple(sv.shape) != (B, D):
+            raise RuntimeError('get_params_gt_reenacted: shift_vector must be [%d,%d], got %s' % (B, D, tuple(sv.shape)))
+        pose_gt, exp_gt = torch.empty_like(ps), torch.empty_like(es)
+        N.call('sgdfr_gt_reenacted_f32', N.ptr(ps.detach()), N.ptr(es.detach()), N.ptr(ang.detach()), N.ptr(pt.detach()),
+               N.ptr(et.detach()), ps.shape[1], es.shape[1], N.ptr(sv.detach()), N.ptr(which), float(self.shift_scale),
+               self._table_train, D, N.ptr(pose_gt), N.ptr(exp_gt), B, N.stream())
+        return {'pose': pose_gt, 'exp': exp_gt}
