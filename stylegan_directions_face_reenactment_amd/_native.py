@@ -217,6 +217,20 @@ DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTY
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
 OPTIONAL_SIGNATURES = {'sgdfr_mfma_ceiling_probe': [_i, _i, _i, _i, _i, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]}
 
+# size queries: name -> number of int arguments; every one returns int64_t, negative for a shape the kernels do not take
+SIZE_QUERIES = {
+    'sgdfr_modconv_prepack_split_elems': 2, 'sgdfr_modconv_prepack_wsplit_elems': 3,
+    'sgdfr_lpips_pack_elems': 0, 'sgdfr_lpips_feature_elems': 3, 'sgdfr_lpips_workspace_bytes': 3,
+    'sgdfr_idloss_pack_elems': 0, 'sgdfr_idloss_saved_elems': 1, 'sgdfr_idloss_workspace_bytes': 3,
+    'sgdfr_flame_pack_elems': 0, 'sgdfr_flame_saved_elems': 1, 'sgdfr_flame_workspace_bytes': 1,
+    'sgdfr_deca_pack_elems': 0, 'sgdfr_deca_saved_elems': 1, 'sgdfr_deca_debug_elems': 1, 'sgdfr_deca_workspace_bytes': 3,
+    'sgdfr_fan_pack_elems': 0, 'sgdfr_fan_debug_elems': 1, 'sgdfr_fan_workspace_bytes': 3,
+    'sgdfr_s3fd_pack_elems': 0, 'sgdfr_s3fd_debug_elems': 3, 'sgdfr_s3fd_map_elems': 3, 'sgdfr_s3fd_workspace_bytes': 3,
+    'sgdfr_e4e_pack_elems': 1, 'sgdfr_e4e_debug_elems': 2, 'sgdfr_e4e_workspace_bytes': 2,
+    'sgdfr_facecrop_workspace_bytes': 4,
+}
+COUNT_QUERIES = ('sgdfr_e4e_style_count', 'sgdfr_e4e_param_count')      # int (int R): a count, or -1 for a resolution out of range
+
 MODE_PLAIN3, MODE_UP3, MODE_DOWN3 = 0, 1, 2
 SPLIT_BF16, SPLIT_FP16, SPLIT_FP16F8 = 0, 1, 2      # include/sgdfr.h SGDFR_SPLIT_*
 ACT_NONE, ACT_LRELU = 0, 1
@@ -238,54 +252,12 @@ def load():
     lib.sgdfr_last_error.restype = ctypes.c_char_p
     lib.sgdfr_split_saturation_count.argtypes = [ctypes.c_int]
     lib.sgdfr_split_saturation_count.restype = ctypes.c_longlong
-    lib.sgdfr_modconv_prepack_split_elems.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.sgdfr_modconv_prepack_split_elems.restype = ctypes.c_int64
-    lib.sgdfr_modconv_prepack_wsplit_elems.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.sgdfr_modconv_prepack_wsplit_elems.restype = ctypes.c_int64
-    lib.sgdfr_lpips_pack_elems.argtypes = []
-    lib.sgdfr_lpips_pack_elems.restype = ctypes.c_int64
-    for name in ('sgdfr_lpips_feature_elems', 'sgdfr_lpips_workspace_bytes'):
-        getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    for name, nargs in SIZE_QUERIES.items():
+        getattr(lib, name).argtypes = [ctypes.c_int] * nargs
         getattr(lib, name).restype = ctypes.c_int64
-    lib.sgdfr_idloss_pack_elems.argtypes = []
-    lib.sgdfr_idloss_pack_elems.restype = ctypes.c_int64
-    lib.sgdfr_idloss_saved_elems.argtypes = [ctypes.c_int]
-    lib.sgdfr_idloss_saved_elems.restype = ctypes.c_int64
-    lib.sgdfr_idloss_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.sgdfr_idloss_workspace_bytes.restype = ctypes.c_int64
-    lib.sgdfr_flame_pack_elems.argtypes = []
-    lib.sgdfr_flame_pack_elems.restype = ctypes.c_int64
-    for name in ('sgdfr_flame_saved_elems', 'sgdfr_flame_workspace_bytes'):
-        getattr(lib, name).argtypes = [ctypes.c_int]
-        getattr(lib, name).restype = ctypes.c_int64
-    lib.sgdfr_deca_pack_elems.argtypes = []
-    lib.sgdfr_deca_pack_elems.restype = ctypes.c_int64
-    for name in ('sgdfr_deca_saved_elems', 'sgdfr_deca_debug_elems'):
-        getattr(lib, name).argtypes = [ctypes.c_int]
-        getattr(lib, name).restype = ctypes.c_int64
-    lib.sgdfr_deca_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.sgdfr_deca_workspace_bytes.restype = ctypes.c_int64
-    lib.sgdfr_fan_pack_elems.argtypes = []
-    lib.sgdfr_fan_pack_elems.restype = ctypes.c_int64
-    lib.sgdfr_fan_debug_elems.argtypes = [ctypes.c_int]
-    lib.sgdfr_fan_debug_elems.restype = ctypes.c_int64
-    lib.sgdfr_fan_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.sgdfr_fan_workspace_bytes.restype = ctypes.c_int64
-    lib.sgdfr_s3fd_pack_elems.argtypes = []
-    lib.sgdfr_s3fd_pack_elems.restype = ctypes.c_int64
-    for name in ('sgdfr_s3fd_debug_elems', 'sgdfr_s3fd_map_elems', 'sgdfr_s3fd_workspace_bytes'):
-        getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        getattr(lib, name).restype = ctypes.c_int64
-    for name in ('sgdfr_e4e_style_count', 'sgdfr_e4e_param_count'):      # a count, or -1 for a resolution out of range
+    for name in COUNT_QUERIES:
         getattr(lib, name).argtypes = [ctypes.c_int]
         getattr(lib, name).restype = ctypes.c_int
-    lib.sgdfr_e4e_pack_elems.argtypes = [ctypes.c_int]
-    lib.sgdfr_e4e_pack_elems.restype = ctypes.c_int64
-    for name in ('sgdfr_e4e_debug_elems', 'sgdfr_e4e_workspace_bytes'):
-        getattr(lib, name).argtypes = [ctypes.c_int, ctypes.c_int]
-        getattr(lib, name).restype = ctypes.c_int64
-    lib.sgdfr_facecrop_workspace_bytes.argtypes = [ctypes.c_int] * 4
-    lib.sgdfr_facecrop_workspace_bytes.restype = ctypes.c_int64
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():
@@ -306,6 +278,20 @@ def call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise RuntimeError('%s failed (%d): %s' % (name, rc, lib.sgdfr_last_error().decode()))
+
+
+def size(query, *dims, error):
+    """The answer of a size query (SIZE_QUERIES); ValueError(error) where the kernels do not take the shape."""
+    n = getattr(load(), query)(*dims)
+    if n < 0:
+        raise ValueError(error)
+    return n
+
+
+def workspace(query, device, *dims, error):
+    """(float32 tensor, nbytes) for a `*_workspace_bytes` query; ValueError(error) where the kernels do not take the shape."""
+    nbytes = size(query, *dims, error=error)
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
 
 
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)

@@ -18,13 +18,13 @@ changes.  The 'kpt68' boxes come in as numbers: landmarks.get_landmarks -> landm
 caller's face boxes (the S3FD face detector itself stays with the caller), and a row the detector failed on is the caller's
 business (the reference zeroes its coefficients and sets its angles to -180).  E_detail is not built.
 """
-import ctypes
 from collections import OrderedDict
 
 import torch
 from torch import nn
 
 from . import _native as N
+from .packs import PackedWeights, views
 
 OUTSIZE = 236
 CROP = 224
@@ -70,8 +70,13 @@ class _ResNet(nn.Module):
                 yield b
 
 
-class ResnetEncoder(nn.Module):
+class ResnetEncoder(PackedWeights, nn.Module):
     """encoders.ResnetEncoder(outsize=236): weights only.  forward(images, M) -> [B,236] parameters on the HIP kernels."""
+    PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_deca_prepack_f32', 'sgdfr_deca_pack_elems', N.DECA_PARAMS
+    TRAIN_ERROR = ('ResnetEncoder: the HIP kernels run the encoder in eval mode only (running BatchNorm statistics); '
+                   'call .eval()')
+    GRAD_ERROR = ('ResnetEncoder: the HIP kernels give no gradient for the encoder weights; keep every parameter at '
+                  'requires_grad=False')
 
     def __init__(self, outsize=OUTSIZE, last_op=None):
         if outsize != OUTSIZE or last_op is not None:
@@ -82,16 +87,8 @@ class ResnetEncoder(nn.Module):
         self.layers = nn.Sequential(nn.Linear(2048, 1024), nn.ReLU(), nn.Linear(1024, outsize))
         for p in self.parameters():
             p.requires_grad = False
-        self._pack = None
 
     # ---- weights
-    def _key(self):
-        return tuple((t.data_ptr(), t._version, t.device) for t in self.state_dict(keep_vars=True).values())
-
-    def invalidate_packs(self):
-        """Drop the weight pack (needed only after in-place writes through `.data`, which bump no version counter)."""
-        self._pack = None
-
     def folded(self, dtype=torch.float32):
         """The 134 tensors sgdfr_deca_prepack_f32 takes (None for the projection of an identity block), every BatchNorm folded
         in fp64 on the parameters' device, returned in `dtype`."""
@@ -115,43 +112,6 @@ class ResnetEncoder(nn.Module):
         for lin in (self.layers[0], self.layers[2]):
             out += [lin.weight.detach().double(), lin.bias.detach().double()]
         return [None if v is None else v.to(dtype).contiguous() for v in out]
-
-    def packed(self):
-        """The device weight pack of sgdfr_deca_prepack_f32, rebuilt when any parameter's or buffer's storage or version changes."""
-        key = self._key()
-        if self._pack is None or self._pack[0] != key:
-            ps = self.folded()
-            for p in ps:
-                N.require_device(p)
-            dev = self.layers[0].weight.device
-            pack = torch.empty(N.load().sgdfr_deca_pack_elems(), dtype=torch.float32, device=dev)
-            arr = (ctypes.c_void_p * N.DECA_PARAMS)(*[None if p is None else p.data_ptr() for p in ps])
-            N.call('sgdfr_deca_prepack_f32', arr, N.ptr(pack), N.stream())
-            self._pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
-        return self._pack[1]
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packs()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        res = super().load_state_dict(OrderedDict(state_dict), strict=strict, **kwargs)
-        self.invalidate_packs()
-        return res
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_pack'] = None
-        return state
-
-    def check(self):
-        if self.training:
-            raise RuntimeError('ResnetEncoder: the HIP kernels run the encoder in eval mode only (running BatchNorm statistics); '
-                               'call .eval()')
-        if any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError('ResnetEncoder: the HIP kernels give no gradient for the encoder weights; keep every parameter at '
-                               'requires_grad=False')
 
     def forward(self, images, M):
         return run(self, images, M)[0]
@@ -194,24 +154,13 @@ def crop_matrix(bbox, src_hw, align_corners=False, dtype=torch.float32):
 
 
 def _workspace(rows, H, W, device):
-    nbytes = N.load().sgdfr_deca_workspace_bytes(rows, H, W)
-    if nbytes < 0:
-        raise ValueError('deca: unsupported batch of %d images of %dx%d' % (rows, H, W))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+    return N.workspace('sgdfr_deca_workspace_bytes', device, rows, H, W,
+                       error='deca: unsupported batch of %d images of %dx%d' % (rows, H, W))
 
 
 def debug_views(debug, rows):
     """The debug buffer as named views (csrc/deca.hip's DebugLayout): stem, pool, first / last (per stage), feat."""
-    out, o = {'first': [], 'last': []}, 0
-
-    def take(shape):
-        nonlocal o
-        n = rows
-        for d in shape:
-            n *= d
-        v = debug[o:o + n].view(rows, *shape)
-        o += n
-        return v
+    out, take = {'first': [], 'last': []}, views(debug, rows)
 
     out['stem'] = take((64, 112, 112))
     out['pool'] = take((64, 56, 56))
@@ -220,23 +169,14 @@ def debug_views(debug, rows):
         out['first'].append(take(shape))
         out['last'].append(take(shape))
     out['feat'] = take((2048,))
-    assert o == debug.numel(), (o, debug.numel())
+    take.done()
     return out
 
 
 def saved_views(saved, rows):
     """The saved bytes of a forward with `rows` rows as named uint8 views (csrc/deca.hip's SavedLayout): stem (ReLU mask), arg
     (max-pool choice kh * 3 + kw), per bottleneck m1, m2, m3 (ReLU masks after conv1, conv2 and the sum), fc (regressor mask)."""
-    out, o = {'m1': [], 'm2': [], 'm3': []}, 0
-
-    def take(shape):
-        nonlocal o
-        n = rows
-        for d in shape:
-            n *= d
-        v = saved[o:o + n].view(rows, *shape)
-        o = (o + n + 63) & ~63
-        return v
+    out, take = {'m1': [], 'm2': [], 'm3': []}, views(saved, rows, align=64)
 
     out['stem'] = take((64, 112, 112))
     out['arg'] = take((64, 56, 56))
@@ -249,7 +189,7 @@ def saved_views(saved, rows):
             out['m3'].append(take((4 * planes, ho, ho)))
             h = ho
     out['fc'] = take((1024,))
-    assert o == saved.numel(), (o, saved.numel())
+    take.done()
     return out
 
 

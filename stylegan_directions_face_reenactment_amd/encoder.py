@@ -21,7 +21,6 @@ specific to this build:
 Beside that, `encode(enc, images)` runs the whole encoder on the hand-written kernels of csrc/e4e.hip (exact-f32 MFMA implicit
 GEMM, forward only, one stream, no host synchronisation); `Encoder4Editing.forward` itself stays on the MIOpen plan.
 """
-import ctypes
 import math
 from collections import OrderedDict
 
@@ -31,6 +30,7 @@ from torch import nn
 
 from . import _native as N
 from .model import EqualLinear
+from .packs import PackedWeights, views
 
 # (depth, units) of the four trunk stages; the first unit of a stage has stride 2 (helpers.py:29-36, num_layers=50)
 _TRUNK = {50: ((64, 3), (128, 4), (256, 14), (512, 3)),
@@ -96,7 +96,12 @@ def _fold(conv, bn):
     return (conv.weight * g.view(-1, 1, 1, 1)).contiguous(memory_format=torch.channels_last), bn.bias - bn.running_mean * g
 
 
-class Encoder4Editing(nn.Module):
+class Encoder4Editing(PackedWeights, nn.Module):
+    PREPACK, PACK_ELEMS = 'sgdfr_e4e_prepack_f32', 'sgdfr_e4e_pack_elems'
+    TRAIN_ERROR = 'encode: the module is in train() mode; the HIP path folds the BatchNorm statistics, call .eval() first'
+    # no GRAD_ERROR: the module's own forward trains; encode() is forward only and returns no graph
+    WRAP_STATE_DICT = False         # a checkpoint's `_metadata` decides how its BatchNorms load: the dict is passed on as it comes
+
     def __init__(self, num_layers, mode='ir', image_resolution=256):
         super().__init__()
         if num_layers not in _TRUNK:
@@ -121,7 +126,6 @@ class Encoder4Editing(nn.Module):
         self.latlayer1 = nn.Conv2d(256, 512, 1)
         self.latlayer2 = nn.Conv2d(128, 512, 1)
         self._plan_key, self._plan = None, None
-        self._hip_pack = None       # (state key, device pack of csrc/e4e.hip, the folded tensors): see packed()
 
     # ------------------------------------------------------------------ reference-shaped (autograd-capable) forward
     def _features(self, x):
@@ -158,24 +162,26 @@ class Encoder4Editing(nn.Module):
         return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
     def invalidate_packs(self):
-        """Drop the folded inference plan and the HIP weight pack (needed only after in-place `.data` edits, which the version
-        counters behind `_state_key` do not see)."""
+        """Drop the folded inference plan with the HIP weight pack (needed only after in-place `.data` edits, which the version
+        counters behind `_state_key` and `_key` do not see)."""
         self._plan_key, self._plan = None, None
-        self._hip_pack = None
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_hip_pack'] = None       # rebuilt on demand: never copied, never pickled
-        return state
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packs()
-        return out
+        super().invalidate_packs()
 
     def _load_from_state_dict(self, *args, **kwargs):
+        """Also drops the packs when the encoder is loaded as a part of a larger module, whose load_state_dict is not ours."""
         super()._load_from_state_dict(*args, **kwargs)
         self.invalidate_packs()
+
+    def folded(self, dtype=torch.float32):
+        return folded(self, dtype)
+
+    def _prepack_plan(self, ps):
+        R, lib = self.image_resolution, N.load()
+        count = lib.sgdfr_e4e_param_count(R)
+        if count != len(ps) or lib.sgdfr_e4e_style_count(R) != self.style_count:
+            raise RuntimeError('encode: %d folded tensors and %d heads, the kernels expect %d and %d at resolution %d' % (
+                len(ps), self.style_count, count, lib.sgdfr_e4e_style_count(R), R))
+        return count, (R,), (R,)
 
     def _build_plan(self):
         cl = torch.channels_last
@@ -302,8 +308,7 @@ def _check_module(enc):
     if enc.mode != 'ir_se' or enc.num_layers != 50:
         raise ValueError("encode: the HIP path runs Encoder4Editing(50, 'ir_se', R) only, got (%r, %r); use the module's own "
                          'forward for the other trunks' % (enc.num_layers, enc.mode))
-    if enc.training:
-        raise RuntimeError('encode: the module is in train() mode; the HIP path folds the BatchNorm statistics, call .eval() first')
+    enc.check()
     R = enc.image_resolution
     if not isinstance(R, int) or R % 16 or not 32 <= R <= 256:
         raise ValueError('encode: resolution %r is not a multiple of 16 in 32..256 (every style head must end at 1x1)' % (R,))
@@ -312,29 +317,12 @@ def _check_module(enc):
 
 def packed(enc):
     """The device weight pack of sgdfr_e4e_prepack_f32, rebuilt when any parameter's or buffer's storage or version changes."""
-    key = enc._state_key()
-    if enc._hip_pack is None or enc._hip_pack[0] != key:
-        R = enc.image_resolution
-        lib = N.load()
-        ps = folded(enc)
-        for p in ps:
-            N.require_device(p)
-        count = lib.sgdfr_e4e_param_count(R)
-        if count != len(ps) or lib.sgdfr_e4e_style_count(R) != enc.style_count:
-            raise RuntimeError('encode: %d folded tensors and %d heads, the kernels expect %d and %d at resolution %d' % (
-                len(ps), enc.style_count, count, lib.sgdfr_e4e_style_count(R), R))
-        pack = torch.empty(lib.sgdfr_e4e_pack_elems(R), dtype=torch.float32, device=enc.latlayer1.weight.device)
-        arr = (ctypes.c_void_p * count)(*[None if p is None else p.data_ptr() for p in ps])
-        N.call('sgdfr_e4e_prepack_f32', arr, R, N.ptr(pack), N.stream())
-        enc._hip_pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
-    return enc._hip_pack[1]
+    return enc.packed()
 
 
 def _workspace(rows, R, device):
-    nbytes = N.load().sgdfr_e4e_workspace_bytes(rows, R)
-    if nbytes < 0:
-        raise ValueError('encode: unsupported batch of %d images at resolution %d (1..256 rows, rows*R*R <= 2^24)' % (rows, R))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+    return N.workspace('sgdfr_e4e_workspace_bytes', device, rows, R,
+                       error='encode: unsupported batch of %d images at resolution %d (1..256 rows, rows*R*R <= 2^24)' % (rows, R))
 
 
 def debug_views(debug, rows, R, style_count):
@@ -342,14 +330,11 @@ def debug_views(debug, rows, R, style_count):
     EqualLinears as h_coarse [B,3,512], h_middle [B,4,512], h_fine [B,style_count-7,512]."""
     shapes = (('stem', 64, R), ('u0', 64, R // 2), ('u3', 128, R // 4), ('c1', 128, R // 4), ('c2', 256, R // 8), ('c3', 512, R // 16),
               ('p2', 512, R // 8), ('p1', 512, R // 4))
-    out, o = OrderedDict(), 0
+    out, cut = OrderedDict(), views(debug, rows)
     for name, ch, side in shapes:
-        n = rows * ch * side * side
-        out[name] = debug[o:o + n].view(rows, ch, side, side)
-        o += n
-    h = debug[o:o + rows * style_count * 512].view(rows, style_count, 512)
-    o += h.numel()
-    assert o == debug.numel(), (o, debug.numel())
+        out[name] = cut((ch, side, side))
+    h = cut((style_count, 512))
+    cut.done()
     out['h_coarse'], out['h_middle'], out['h_fine'] = h[:, :3], h[:, 3:7], h[:, 7:]
     return out
 

@@ -62,10 +62,9 @@ def _workspace(B, H, W, max_size, device):
     key = (B, H, W, max_size, device)
     hit = _workspaces.get(key)
     if hit is None:
-        nbytes = N.load().sgdfr_facecrop_workspace_bytes(B, H, W, max_size)
-        if nbytes < 0:
-            raise ValueError('face_crop: unsupported batch of %d frames of %dx%d with max_size %d (1..1024 rows, sides and max_size '
-                             '1..4096)' % (B, H, W, max_size))
+        nbytes = N.size('sgdfr_facecrop_workspace_bytes', B, H, W, max_size,
+                        error='face_crop: unsupported batch of %d frames of %dx%d with max_size %d (1..1024 rows, sides and max_size '
+                              '1..4096)' % (B, H, W, max_size))
         hit = _workspaces[key] = (torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes)
     return hit
 

@@ -26,6 +26,7 @@ from torch import nn
 
 from . import _native as N
 from . import landmarks as L
+from .packs import PackedWeights, views
 
 LEVELS = 6
 CAPACITY = 1024
@@ -47,8 +48,12 @@ class L2Norm(nn.Module):
         self.weight = nn.Parameter(torch.full((n_channels,), float(scale)))
 
 
-class S3FD(nn.Module):
+class S3FD(PackedWeights, nn.Module):
     """net_s3fd.s3fd: weights only.  forward(images [B,3,H,W], 0..255) -> the twelve maps [cls1, reg1, ..., cls6, reg6]."""
+    PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_s3fd_prepack_f32', 'sgdfr_s3fd_pack_elems', N.S3FD_PARAMS
+    # no TRAIN_ERROR: the network has no BatchNorm and no Dropout, train mode changes nothing
+    GRAD_ERROR = ('S3FD: the HIP kernels are forward only and give no gradient for the weights; keep every parameter at '
+                  'requires_grad=False')
 
     def __init__(self):
         super().__init__()
@@ -68,16 +73,8 @@ class S3FD(nn.Module):
             self.add_module(name + '_mbox_loc', c(ch, 4, 3, 1, 1))
         for p in self.parameters():
             p.requires_grad = False
-        self._pack = None
 
     # ---- weights
-    def _key(self):
-        return tuple((t.data_ptr(), t._version, t.device) for t in self.state_dict(keep_vars=True).values())
-
-    def invalidate_packs(self):
-        """Drop the weight pack (needed only after in-place writes through `.data`, which bump no version counter)."""
-        self._pack = None
-
     def folded(self, dtype=torch.float32):
         """The 50 tensors sgdfr_s3fd_prepack_f32 takes: the 19 trunk convs' w, b, then per level conf and loc concatenated to one
         conv's w [conf+4,C,3,3], b [conf+4], the L2Norm weight of levels 0-2 folded in per input channel in fp64."""
@@ -92,39 +89,6 @@ class S3FD(nn.Module):
                 w = w * getattr(self, name).weight.detach().double().view(1, -1, 1, 1)
             out += [w, torch.cat([conf.bias.detach().double(), loc.bias.detach().double()], 0)]
         return [v.to(dtype).contiguous() for v in out]
-
-    def packed(self):
-        """The device weight pack of sgdfr_s3fd_prepack_f32, rebuilt when any parameter's storage or version changes."""
-        key = self._key()
-        if self._pack is None or self._pack[0] != key:
-            ps = self.folded()
-            for p in ps:
-                N.require_device(p)
-            pack = torch.empty(N.load().sgdfr_s3fd_pack_elems(), dtype=torch.float32, device=self.conv1_1.weight.device)
-            arr = (ctypes.c_void_p * N.S3FD_PARAMS)(*[p.data_ptr() for p in ps])
-            N.call('sgdfr_s3fd_prepack_f32', arr, N.ptr(pack), N.stream())
-            self._pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
-        return self._pack[1]
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packs()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        res = super().load_state_dict(OrderedDict(state_dict), strict=strict, **kwargs)
-        self.invalidate_packs()
-        return res
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_pack'] = None
-        return state
-
-    def check(self):
-        if any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError('S3FD: the HIP kernels are forward only and give no gradient for the weights; keep every parameter at '
-                               'requires_grad=False')
 
     def forward(self, images):
         return network(self, images)
@@ -157,22 +121,16 @@ def level_dims(H, W):
 
 
 def _workspace(rows, H, W, device):
-    nbytes = N.load().sgdfr_s3fd_workspace_bytes(rows, H, W)
-    if nbytes < 0:
-        raise ValueError('face_detector: unsupported batch of %d images of %dx%d (1..256 rows, each side 32..4096, rows*H*W <= 2^24)'
-                         % (rows, H, W))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+    return N.workspace('sgdfr_s3fd_workspace_bytes', device, rows, H, W,
+                       error='face_detector: unsupported batch of %d images of %dx%d (1..256 rows, each side 32..4096, '
+                             'rows*H*W <= 2^24)' % (rows, H, W))
 
 
 def map_views(maps, rows, H, W):
     """The flat map buffer as the twelve tensors of s3fd.forward: cls1 [B,2,h,w], reg1 [B,4,h,w], ..."""
-    out, o = [], 0
-    for h, w in level_dims(H, W):
-        for c in (2, 4):
-            n = rows * c * h * w
-            out.append(maps[o:o + n].view(rows, c, h, w))
-            o += n
-    assert o == maps.numel(), (o, maps.numel())
+    cut = views(maps, rows)
+    out = [cut((c, h, w)) for h, w in level_dims(H, W) for c in (2, 4)]
+    cut.done()
     return out
 
 
@@ -185,18 +143,12 @@ def debug_views(debug, rows, H, W):
     sizes['conv2_2'] = (h // 2, w // 2)
     sizes['conv3_3'], sizes['conv4_3'], sizes['conv5_3'], sizes['fc7'], sizes['conv6_2'], sizes['conv7_2'] = dims
     sizes['fc6'] = dims[3]
-    out, o = OrderedDict(), 0
+    out, cut = OrderedDict(), views(debug, rows)
     for name, ch in DEBUG_TAPS:
-        hh, ww = sizes[name]
-        n = rows * ch * hh * ww
-        out[name] = debug[o:o + n].view(rows, ch, hh, ww)
-        o += n
+        out[name] = cut((ch,) + sizes[name])
     for l, name in enumerate(('rnorm3', 'rnorm4', 'rnorm5')):
-        hh, ww = dims[l]
-        n = rows * hh * ww
-        out[name] = debug[o:o + n].view(rows, hh, ww)
-        o += n
-    assert o == debug.numel(), (o, debug.numel())
+        out[name] = cut(dims[l])
+    cut.done()
     return out
 
 

@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from . import _native as N
+from .packs import PackedWeights
 
 V, FACES, N_SHAPE, N_EXP, N_POSE_FEATURE, JOINTS, LANDMARKS, DYN_ROWS, DYN_LMK, STATIC_LMK = 5023, 9976, 100, 50, 36, 5, 68, 79, 17, 51
 N_CSR = (STATIC_LMK + LANDMARKS + DYN_ROWS * DYN_LMK) * 3
@@ -43,9 +44,13 @@ def _to_np(a, dtype):
     return np.array(a, dtype=dtype)
 
 
-class FLAME(nn.Module):
+class FLAME(PackedWeights, nn.Module):
     """models/FLAME.py's module at DECA's sizes (n_shape = 100, n_exp = 50): buffers under the reference's names, so its state dict
     loads; forward(shape_params, expression_params, pose_params) -> (vertices [B,5023,3], landmarks2d [B,68,3], landmarks3d [B,68,3])."""
+    PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_flame_prepack_f32', 'sgdfr_flame_pack_elems', N.FLAME_PARAMS
+    PACK_DTYPE = None               # the folded list mixes int32 index tables with float32: only the device is checked
+    WRAP_STATE_DICT = False         # the dict is passed on as it comes (buffers only: no BatchNorm whose loading the wrap changes)
+    # no TRAIN_ERROR, no GRAD_ERROR: nothing calls check(); the tables are buffers and the two pose parameters must be zero (folded())
 
     def __init__(self, n_shape=N_SHAPE, n_exp=N_EXP, n_vertices=V, n_faces=FACES):
         if (n_shape, n_exp, n_vertices, n_faces) != (N_SHAPE, N_EXP, V, FACES):
@@ -58,7 +63,6 @@ class FLAME(nn.Module):
         self.neck_kin_chain.copy_(torch.tensor([1, 0]))
         self.register_parameter('eye_pose', nn.Parameter(torch.zeros(1, 6), requires_grad=False))
         self.register_parameter('neck_pose', nn.Parameter(torch.zeros(1, 3), requires_grad=False))
-        self._pack = None
 
     @classmethod
     def from_files(cls, flame_model_path, flame_lmk_embedding_path, n_shape=N_SHAPE, n_exp=N_EXP):
@@ -98,13 +102,6 @@ class FLAME(nn.Module):
         return self
 
     # ---- tables
-    def _key(self):
-        return tuple((t.data_ptr(), t._version, t.device) for t in self.state_dict(keep_vars=True).values())
-
-    def invalidate_packs(self):
-        """Drop the device pack (needed only after in-place writes through `.data`, which bump no version counter)."""
-        self._pack = None
-
     def folded(self):
         """The 15 tensors sgdfr_flame_prepack_f32 takes, on the buffers' device: the joint regressor folded in fp64, landmark faces
         resolved to corner vertices, and the inverse landmark index (per vertex, the landmark corners that reference it)."""
@@ -146,35 +143,8 @@ class FLAME(nn.Module):
                 i32(corner[0]), f(bary[0]), i32(corner[1]), f(bary[1]), i32(corner[2]), f(bary[2]),
                 i32(offsets), i32(slots), f(torch.from_numpy(weights[order]))]
 
-    def packed(self):
-        """The device pack of sgdfr_flame_prepack_f32, rebuilt when any buffer's storage or version changes."""
-        key = self._key()
-        if self._pack is None or self._pack[0] != key:
-            ps = self.folded()
-            for p in ps:
-                if not p.is_cuda:
-                    raise RuntimeError('expected a GPU (HIP) tensor, got device %s: this package has no CPU path' % p.device)
-            pack = torch.empty(N.load().sgdfr_flame_pack_elems(), dtype=torch.float32, device=ps[0].device)
-            arr = (ctypes.c_void_p * N.FLAME_PARAMS)(*[p.data_ptr() for p in ps])
-            N.call('sgdfr_flame_prepack_f32', arr, V, N_SHAPE + N_EXP, N_POSE_FEATURE, JOINTS, DYN_ROWS, int(ps[13].numel()), N.ptr(pack),
-                   N.stream())
-            self._pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
-        return self._pack[1]
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packs()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        res = super().load_state_dict(state_dict, strict=strict, **kwargs)
-        self.invalidate_packs()
-        return res
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_pack'] = None
-        return state
+    def _prepack_plan(self, ps):
+        return self.PARAMS, (), (V, N_SHAPE + N_EXP, N_POSE_FEATURE, JOINTS, DYN_ROWS, int(ps[13].numel()))
 
     def forward(self, shape_params=None, expression_params=None, pose_params=None, eye_pose_params=None):
         if eye_pose_params is not None:
@@ -197,16 +167,11 @@ def _check_coeffs(shape, exp, pose, cam=None):
 
 
 def _workspace(rows, device):
-    nbytes = N.load().sgdfr_flame_workspace_bytes(rows)
-    if nbytes < 0:
-        raise ValueError('FLAME: unsupported batch of %d rows' % rows)
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device), nbytes
+    return N.workspace('sgdfr_flame_workspace_bytes', device, rows, error='FLAME: unsupported batch of %d rows' % rows)
 
 
 def _saved(rows, device):
-    n = N.load().sgdfr_flame_saved_elems(rows)
-    if n < 0:
-        raise ValueError('FLAME: unsupported batch of %d rows' % rows)
+    n = N.size('sgdfr_flame_saved_elems', rows, error='FLAME: unsupported batch of %d rows' % rows)
     return torch.empty(n, dtype=torch.float32, device=device)
 
 
@@ -332,7 +297,7 @@ class ShapeLoss(nn.Module):
             self._cam = torch.tensor([8.0, 0.0, 0.0], dtype=torch.float32).repeat(2 * rows, 1).to(device)
         return self._cam
 
-    def __getstate__(self):
+    def __getstate__(self):         # ShapeLoss holds no pack (the FLAME module does): this drops its cached camera rows only
         state = self.__dict__.copy()
         state['_cam'] = None
         return state

@@ -17,7 +17,6 @@ y's embeddings.  The cosine and the mean stay in torch on [B,512] (nn.CosineSimi
 it), so autograd supplies dL/de.  Every BatchNorm is folded into the weights on the host in fp64, once per weight version; the
 device pack (forward and input-gradient weights, ~2 x 175 MB) is rebuilt whenever a parameter's storage or version changes.
 """
-import ctypes
 from collections import OrderedDict
 
 import torch
@@ -25,13 +24,19 @@ from torch import nn
 
 from . import _native as N
 from .encoder import ResidualUnit, _TRUNK
+from .packs import PackedWeights, views
 
 EMB = 512
 
 
-class Backbone(nn.Module):
+class Backbone(PackedWeights, nn.Module):
     """model_irse.Backbone(input_size=112, num_layers=50, mode='ir_se', drop_ratio=0.6): weights only.  forward(x) runs the HIP
     kernels on [B,3,112,112] faces (AdaptiveAvgPool2d(112) is the identity there), returning l2-normalised [B,512] embeddings."""
+    PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_idloss_prepack_f32', 'sgdfr_idloss_pack_elems', N.IDLOSS_PARAMS
+    TRAIN_ERROR = ('IDLoss: the HIP kernels run the facenet in eval mode only (running BatchNorm statistics); '
+                   'call facenet.eval()')
+    GRAD_ERROR = ('IDLoss: the HIP kernels give no gradient for the facenet weights; keep every parameter at '
+                  'requires_grad=False (the reference never reads them)')
 
     def __init__(self, input_size=112, num_layers=50, mode='ir_se', drop_ratio=0.6, affine=True):
         if (input_size, num_layers, mode, affine) != (112, 50, 'ir_se', True):
@@ -49,16 +54,8 @@ class Backbone(nn.Module):
         self.body = nn.Sequential(*units)
         for p in self.parameters():
             p.requires_grad = False
-        self._pack = None
 
     # ---- weights
-    def _key(self):
-        return tuple((t.data_ptr(), t._version, t.device) for t in self.state_dict(keep_vars=True).values())
-
-    def invalidate_packs(self):
-        """Drop the weight pack (needed only after in-place writes through `.data`, which bump no version counter)."""
-        self._pack = None
-
     def folded(self, dtype=torch.float32):
         """The 245 tensors sgdfr_idloss_prepack_f32 takes (None for the shortcut conv of an identity unit), every BatchNorm
         folded in fp64 on the parameters' device, returned in `dtype`."""
@@ -92,44 +89,10 @@ class Backbone(nn.Module):
         out += [q.view(-1, 1) * W * sk.view(1, -1), q * (W @ tk + lin.bias.detach().double()) + r]
         return [None if v is None else v.to(dtype).contiguous() for v in out]
 
-    def packed(self):
-        """The device weight pack of sgdfr_idloss_prepack_f32, rebuilt when any parameter's or buffer's storage or version changes."""
-        key = self._key()
-        if self._pack is None or self._pack[0] != key:
-            ps = self.folded()
-            for p in ps:
-                N.require_device(p)
-            dev = self.output_layer[3].weight.device
-            pack = torch.empty(N.load().sgdfr_idloss_pack_elems(), dtype=torch.float32, device=dev)
-            arr = (ctypes.c_void_p * N.IDLOSS_PARAMS)(*[None if p is None else p.data_ptr() for p in ps])
-            N.call('sgdfr_idloss_prepack_f32', arr, N.ptr(pack), N.stream())
-            self._pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
-        return self._pack[1]
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packs()
-        return out
-
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         """model_ir_se50.pth's keys, or the same with an `facenet.` prefix (an IDLoss state dict)."""
         sd = OrderedDict((k[len('facenet.'):] if k.startswith('facenet.') else k, v) for k, v in state_dict.items())
-        res = super().load_state_dict(sd, strict=strict, **kwargs)
-        self.invalidate_packs()
-        return res
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_pack'] = None
-        return state
-
-    def check(self):
-        if self.training:
-            raise RuntimeError('IDLoss: the HIP kernels run the facenet in eval mode only (running BatchNorm statistics); '
-                               'call facenet.eval()')
-        if any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError('IDLoss: the HIP kernels give no gradient for the facenet weights; keep every parameter at '
-                               'requires_grad=False (the reference never reads them)')
+        return super().load_state_dict(sd, strict=strict, **kwargs)
 
     def forward(self, x):
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, 112, 112):
@@ -144,10 +107,7 @@ def _check_image(x, what):
 
 
 def _workspace(rows, H, W, device):
-    nbytes = N.load().sgdfr_idloss_workspace_bytes(rows, H, W)
-    if nbytes < 0:
-        raise ValueError('IDLoss: unsupported image size %dx%d' % (H, W))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+    return N.workspace('sgdfr_idloss_workspace_bytes', device, rows, H, W, error='IDLoss: unsupported image size %dx%d' % (H, W))
 
 
 def _forward(pack, x, y, crop, save):
@@ -205,16 +165,7 @@ def embed(facenet, x, y=None, crop=True):
 def saved_views(saved, rows):
     """The saved buffer of a forward with `rows` x rows as named views (the layout of csrc/idloss.hip's SavedLayout): p0 (stem
     pre-activation), per unit p1 (conv1 output before PReLU), c2 (conv2 + BN2), gate (g [D] then h [D/16] per row), hv (e, |v|)."""
-    out, o = {'p1': [], 'c2': [], 'gate': []}, 0
-
-    def take(shape):
-        nonlocal o
-        n = rows
-        for d in shape:
-            n *= d
-        v = saved[o:o + n].view(rows, *shape)
-        o += n
-        return v
+    out, take = {'p1': [], 'c2': [], 'gate': []}, views(saved, rows)
 
     out['p0'] = take((64, 112, 112))
     c, h = 64, 112
@@ -226,7 +177,7 @@ def saved_views(saved, rows):
             out['gate'].append(take((depth + depth // 16,)))
             c, h = depth, ho
     out['hv'] = take((EMB + 1,))
-    assert o == saved.numel(), (o, saved.numel())
+    take.done()
     return out
 
 

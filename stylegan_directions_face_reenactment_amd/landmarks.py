@@ -22,13 +22,11 @@ against F.interpolate composed that way: the composition itself is UNVERIFIED ag
 Face boxes come in as numbers or as a device tensor; face_detector.py (S3FD on csrc/s3fd.hip) produces them and
 face_detector.detect_landmarks chains the two.  The 3D landmark type (ResNetDepth) and flip_input are not built.
 """
-import ctypes
-from collections import OrderedDict
-
 import torch
 from torch import nn
 
 from . import _native as N
+from .packs import PackedWeights, views
 
 STACKS = 4
 DEPTH = 4
@@ -71,8 +69,12 @@ class _HourGlass(nn.Module):
         self.add_module('b3_%d' % level, _ConvBlock(f, f))
 
 
-class FAN(nn.Module):
+class FAN(PackedWeights, nn.Module):
     """models.FAN(num_modules=4): weights only.  forward(crop [B,3,256,256] in [0,1]) -> the last stack's heatmaps [B,68,64,64]."""
+    PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_fan_prepack_f32', 'sgdfr_fan_pack_elems', N.FAN_PARAMS
+    TRAIN_ERROR = 'FAN: the HIP kernels run the network in eval mode only (running BatchNorm statistics); call .eval()'
+    GRAD_ERROR = ('FAN: the HIP kernels are forward only and give no gradient for the weights; keep every parameter at '
+                  'requires_grad=False')
 
     def __init__(self, num_modules=4):
         if num_modules != STACKS:
@@ -95,16 +97,8 @@ class FAN(nn.Module):
                 self.add_module('al%d' % i, nn.Conv2d(POINTS, 256, 1))
         for p in self.parameters():
             p.requires_grad = False
-        self._pack = None
 
     # ---- weights
-    def _key(self):
-        return tuple((t.data_ptr(), t._version, t.device) for t in self.state_dict(keep_vars=True).values())
-
-    def invalidate_packs(self):
-        """Drop the weight pack (needed only after in-place writes through `.data`, which bump no version counter)."""
-        self._pack = None
-
     def blocks(self):
         """The 59 ConvBlocks in the order sgdfr_fan_prepack_f32 takes them."""
         out = [self.conv2, self.conv3, self.conv4]
@@ -144,42 +138,6 @@ class FAN(nn.Module):
                     bl.bias.detach().double() + al.bias.detach().double()]
         return [None if v is None else v.to(dtype).contiguous() for v in out]
 
-    def packed(self):
-        """The device weight pack of sgdfr_fan_prepack_f32, rebuilt when any parameter's or buffer's storage or version changes."""
-        key = self._key()
-        if self._pack is None or self._pack[0] != key:
-            ps = self.folded()
-            for p in ps:
-                N.require_device(p)
-            dev = self.conv1.weight.device
-            pack = torch.empty(N.load().sgdfr_fan_pack_elems(), dtype=torch.float32, device=dev)
-            arr = (ctypes.c_void_p * N.FAN_PARAMS)(*[None if p is None else p.data_ptr() for p in ps])
-            N.call('sgdfr_fan_prepack_f32', arr, N.ptr(pack), N.stream())
-            self._pack = (key, pack, ps)          # the folded tensors stay alive until the stream has read them
-        return self._pack[1]
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packs()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        res = super().load_state_dict(OrderedDict(state_dict), strict=strict, **kwargs)
-        self.invalidate_packs()
-        return res
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_pack'] = None
-        return state
-
-    def check(self):
-        if self.training:
-            raise RuntimeError('FAN: the HIP kernels run the network in eval mode only (running BatchNorm statistics); call .eval()')
-        if any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError('FAN: the HIP kernels are forward only and give no gradient for the weights; keep every parameter at '
-                               'requires_grad=False')
-
     def forward(self, crop):
         return network(self, crop)
 
@@ -215,32 +173,24 @@ def _prepare(images, faces, input_range):
     return N.f32c(images.detach()), f, code
 
 
+def _unsupported(rows, H, W):
+    return 'landmarks: unsupported batch of %d images of %dx%d' % (rows, H, W)
+
+
 def _workspace(rows, H, W, device):
-    nbytes = N.load().sgdfr_fan_workspace_bytes(rows, H, W)
-    if nbytes < 0:
-        raise ValueError('landmarks: unsupported batch of %d images of %dx%d' % (rows, H, W))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+    return N.workspace('sgdfr_fan_workspace_bytes', device, rows, H, W, error=_unsupported(rows, H, W))
 
 
 def debug_views(debug, rows):
     """The debug buffer as named views (csrc/fan.hip's DebugLayout): stem, conv4, hg (per stack), heatmaps (per stack)."""
-    out, o = {'hg': [], 'heatmaps': []}, 0
-
-    def take(shape):
-        nonlocal o
-        n = rows
-        for d in shape:
-            n *= d
-        v = debug[o:o + n].view(rows, *shape)
-        o += n
-        return v
+    out, take = {'hg': [], 'heatmaps': []}, views(debug, rows)
 
     out['stem'] = take((64, 128, 128))
     out['conv4'] = take((256, MAP, MAP))
     for _ in range(STACKS):
         out['hg'].append(take((256, MAP, MAP)))
         out['heatmaps'].append(take((POINTS, MAP, MAP)))
-    assert o == debug.numel(), (o, debug.numel())
+    take.done()
     return out
 
 
@@ -249,8 +199,7 @@ def crop(images, faces, input_range='255'):
     """The front alone: the window of crop_torch around each face box with zero padding, resized to 256x256, / 255 -> [B,3,256,256]."""
     x, f, code = _prepare(images, faces, input_range)
     B, _, H, W = x.shape
-    if N.load().sgdfr_fan_workspace_bytes(B, H, W) < 0:
-        raise ValueError('landmarks: unsupported batch of %d images of %dx%d' % (B, H, W))
+    N.size('sgdfr_fan_workspace_bytes', B, H, W, error=_unsupported(B, H, W))
     out = torch.empty((B, 3, CROP, CROP), dtype=torch.float32, device=x.device)
     N.call('sgdfr_fan_crop_f32', N.ptr(x), N.ptr(f), B, H, W, code, N.ptr(out), N.stream())
     return out

@@ -10,13 +10,13 @@ every parameter is frozen as in the reference (networks.py:33,85).  The forward 
 as one batch of 2B images; the backward forms dL/dx only.  The library handle stays in _native (modules stay deep-copyable and
 picklable); the weight pack is rebuilt whenever a parameter's storage or version changes, like ModulatedConv2d.packed().
 """
-import ctypes
 from collections import OrderedDict
 
 import torch
 from torch import nn
 
 from . import _native as N
+from .packs import PackedWeights
 
 CHANNELS = (64, 192, 384, 256, 256)
 CONV_INDICES = (0, 3, 6, 8, 10)
@@ -90,18 +90,13 @@ class LpipsTarget:
 
 
 def _workspace(B, H, W, device):
-    nbytes = N.load().sgdfr_lpips_workspace_bytes(B, H, W)
-    if nbytes < 0:
-        raise ValueError('LPIPS: unsupported image size %dx%d' % (H, W))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+    return N.workspace('sgdfr_lpips_workspace_bytes', device, B, H, W, error='LPIPS: unsupported image size %dx%d' % (H, W))
 
 
 def _features(pack, x, y, H, W):
     """Taps of x's rows followed by y's rows (y may be None) -> feature buffer."""
     rows = x.shape[0] + (0 if y is None else y.shape[0])
-    n = N.load().sgdfr_lpips_feature_elems(rows, H, W)
-    if n < 0:
-        raise ValueError('LPIPS: unsupported image size %dx%d' % (H, W))
+    n = N.size('sgdfr_lpips_feature_elems', rows, H, W, error='LPIPS: unsupported image size %dx%d' % (H, W))
     feats = torch.empty(n, dtype=torch.float32, device=x.device)
     ws, nbytes = _workspace(max(x.shape[0], (rows + 1) // 2), H, W, x.device)
     N.call('sgdfr_lpips_features_f32', N.ptr(x), x.shape[0], N.ptr(y), 0 if y is None else y.shape[0], H, W, N.ptr(pack), N.ptr(feats),
@@ -145,10 +140,14 @@ class _LpipsFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
-class LPIPS(nn.Module):
+class LPIPS(PackedWeights, nn.Module):
     r"""Learned Perceptual Image Patch Similarity, AlexNet v0.1 (lpips.py:8-34): forward(x, y) -> scalar
     (1/B) sum over taps and images of the spatially averaged, lin-weighted squared difference of channel-normalised features.
     x, y: [B,3,H,W] fp32 GPU images in [-1,1] (no resize), or y = LPIPS.target(...)."""
+    PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_lpips_prepack_f32', 'sgdfr_lpips_pack_elems', N.LPIPS_PARAMS
+    # no TRAIN_ERROR: the network has no BatchNorm and no Dropout, train mode changes nothing
+    GRAD_ERROR = ('LPIPS: the HIP kernels give no gradient for the LPIPS weights; keep every parameter at '
+                  'requires_grad=False (as the reference does)')
 
     def __init__(self, net_type: str = 'alex', version: str = '0.1'):
         if net_type != 'alex':
@@ -158,42 +157,16 @@ class LPIPS(nn.Module):
         super().__init__()
         self.net = AlexNet()
         self.lin = LinLayers(self.net.n_channels_list)
-        self._pack = None
 
     # ---- weights
-    def _params(self):
+    def folded(self):
+        """The 17 tensors sgdfr_lpips_prepack_f32 takes: nothing is folded, they are the state dict's own entries in the pack's order."""
         L = self.net.layers
         ps = []
         for i in CONV_INDICES:
             ps += [L[i].weight, L[i].bias]
         ps += [self.net.mean, self.net.std] + [self.lin[t][1].weight for t in range(5)]
-        return ps
-
-    def _key(self):
-        return tuple((p.data_ptr(), p._version, p.device) for p in self._params())
-
-    def invalidate_packs(self):
-        """Drop the weight pack (needed only after in-place writes through `.data`, which bump no version counter)."""
-        self._pack = None
-
-    def packed(self):
-        """The device weight pack of sgdfr_lpips_prepack_f32, rebuilt when any parameter's storage or version changes."""
-        key = self._key()
-        if self._pack is None or self._pack[0] != key:
-            ps = [p.detach() for p in self._params()]
-            for p in ps:
-                N.require_device(p)
-            ps = [p.contiguous() for p in ps]
-            pack = torch.empty(N.load().sgdfr_lpips_pack_elems(), dtype=torch.float32, device=ps[0].device)
-            arr = (ctypes.c_void_p * N.LPIPS_PARAMS)(*[p.data_ptr() for p in ps])
-            N.call('sgdfr_lpips_prepack_f32', arr, N.ptr(pack), N.stream())
-            self._pack = (key, pack)
-        return self._pack[1]
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packs()
-        return out
+        return [p.detach().contiguous() for p in ps]
 
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         """Accepts this module's keys, torchvision alexnet's (`features.N.*`) and PerceptualSimilarity's alex.pth
@@ -203,7 +176,7 @@ class LPIPS(nn.Module):
             for k in ('net.mean', 'net.std'):
                 sd.setdefault(k, getattr(self.net, k[4:]))
         if groups == {'net', 'lin'} or not groups:
-            res = super().load_state_dict(sd, strict=strict, **kwargs)
+            return super().load_state_dict(sd, strict=strict, **kwargs)
         else:
             own = self.state_dict()
             prefix = 'net.layers.' if groups == {'net'} else 'lin.'
@@ -213,20 +186,11 @@ class LPIPS(nn.Module):
                 raise RuntimeError('LPIPS.load_state_dict: missing %s, unexpected %s' % (sorted(need - set(sd)), sorted(extra)))
             merged = OrderedDict(own)
             merged.update({k: v for k, v in sd.items() if k in own})
-            res = super().load_state_dict(merged, strict=True, **kwargs)
-        self.invalidate_packs()
-        return res
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state['_pack'] = None
-        return state
+            return super().load_state_dict(merged, strict=True, **kwargs)
 
     # ---- forward
     def _check(self, x):
-        if any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError('LPIPS: the HIP kernels give no gradient for the LPIPS weights; keep every parameter at '
-                               'requires_grad=False (as the reference does)')
+        self.check()
         N.require_device(x)
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError('LPIPS: expected [B,3,H,W] images, got %s' % (tuple(x.shape),))

@@ -141,21 +141,21 @@ def test_encode_refuses_cpu_tensors_train_mode_wrong_sizes_and_other_trunks(smal
 
 def test_pack_stays_out_of_the_state_dict_copies_and_pickles(small):
     enc, state = small
-    enc._hip_pack = ('key', torch.zeros(1), [])
+    enc._pack = ('key', torch.zeros(1), [])
     try:
         assert set(enc.state_dict().keys()) == set(state.keys())
-        assert copy.deepcopy(enc)._hip_pack is None
-        assert pickle.loads(pickle.dumps(enc))._hip_pack is None
+        assert copy.deepcopy(enc)._pack is None
+        assert pickle.loads(pickle.dumps(enc))._pack is None
         enc.invalidate_packs()
-        assert enc._hip_pack is None
-        enc._hip_pack = ('key', torch.zeros(1), [])
+        assert enc._pack is None
+        enc._pack = ('key', torch.zeros(1), [])
         enc.load_state_dict(state, strict=True)
-        assert enc._hip_pack is None
-        enc._hip_pack = ('key', torch.zeros(1), [])
+        assert enc._pack is None
+        enc._pack = ('key', torch.zeros(1), [])
         enc.float()
-        assert enc._hip_pack is None
+        assert enc._pack is None
     finally:
-        enc._hip_pack = None
+        enc._pack = None
 
 
 # ---------------------------------------------------------------------------------------------------------------- the plan rules
