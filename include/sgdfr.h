@@ -32,6 +32,8 @@
  *   sgdfr_gt_reenacted_f32     libs/utilities/utils_train.py:291-374 get_params_gt_reenacted (per-row host loop with one
  *                              device->host read of target_indices there; one launch here), with batch_euler2axis of
  *                              libs/DECA/decalib/utils/rotation_converter.py:306-307
+ *   sgdfr_pairloss_forward_f32 / _backward_f32  libs/utilities/utils_train.py:435-499 calculate_losses_paired: torch_range_1_to_255
+ *                              (libs/utilities/image_utils.py:87-94), the pixel-wise L1 and the latent L1 regulariser
  */
 #ifndef SGDFR_H
 #define SGDFR_H
@@ -449,6 +451,32 @@ int sgdfr_make_shift_random_f32(const float* ang_s, const float* pose_s, const f
 int sgdfr_gt_reenacted_f32(const float* pose_s, const float* exp_s, const float* ang_s, const float* pose_t, const float* exp_t,
                            int pose_dim, int exp_dim, const float* shift, const int* which, float shift_scale,
                            const struct sgdfr_direction* table, int D, float* pose_gt, float* exp_gt, int B, void* stream);
+
+/* The loss arithmetic of the paired training step (libs/utilities/utils_train.py:435-499 calculate_losses_paired), csrc/pairloss.hip:
+ * a mean absolute difference of two contiguous float32 arrays x, y of n elements, with the reference's [-1,1] -> [0,255] image
+ * transform (libs/utilities/image_utils.py:87-94 torch_range_1_to_255) folded in.
+ *   SGDFR_PAIRLOSS_PLAIN:    loss[0] = mean |x - y|                                   (L1Loss(shifted_latents, target_w))
+ *   SGDFR_PAIRLOSS_RANGE255: loss[0] = mean |t(y) - t(x)|, t(v) = (clamp(v,-1,1) + 1) / (2 + 1e-5) * 255, one float32 rounding per
+ *                            operation in that order, true division (losses.py:14-18 on the transformed images); x255 / y255, where
+ *                            not NULL, receive t(x) / t(y) from the same pass (LPIPS reads them).  They must not alias x, y.
+ * sgdfr_pairloss_forward_f32: one streaming launch writes per-block partial sums into `workspace` (at least
+ *   sgdfr_pairloss_workspace_bytes(n) bytes; pass min(n, INT_MAX) to the query, the size no longer grows there), a second launch
+ *   adds them in a fixed order and divides by n.  The grid, the element -> thread assignment and the order of every addition depend
+ *   on n alone, not on the pointers' alignment: two calls on equal data give equal bits.  No atomics, no host synchronisation.
+ * sgdfr_pairloss_backward_f32: one launch, dx[i] =
+ *   PLAIN:    sign(x - y) * (g / n)
+ *   RANGE255: m(x) * ((g255[i] + sign(t(x) - t(y)) * (g / n)) * 255 / (2 + 1e-5)), m(x) = 1 on -1 <= x <= 1 (bounds included) and
+ *             exactly 0 elsewhere (torch's clamp backward), sign(0) = 0 (torch's L1Loss backward); t is recomputed.
+ *   g = grad_loss[0], a DEVICE scalar (NULL: 0); g255 = grad_x255, the upstream gradient of the materialised t(x) (NULL: 0;
+ *   RANGE255 only).  y gets no gradient.  dx may not alias x or y.
+ * 16-byte loads and stores where every pointer of the call is 16-byte aligned, dword accesses of the same elements otherwise. */
+#define SGDFR_PAIRLOSS_PLAIN 0
+#define SGDFR_PAIRLOSS_RANGE255 1
+int64_t sgdfr_pairloss_workspace_bytes(int n);
+int sgdfr_pairloss_forward_f32(const float* x, const float* y, int64_t n, int mode, float* x255, float* y255, float* loss,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_pairloss_backward_f32(const float* x, const float* y, int64_t n, int mode, const float* grad_loss,
+                                const float* grad_x255, float* dx, void* stream);
 
 /* ---- backward helpers (autograd of model.py:232-359 as restated in SURVEY.md Appendix C) ------------------------ */
 

@@ -212,7 +212,10 @@ _u8p = ctypes.c_void_p                   # uint8_t* on the device
 SIGNATURES['sgdfr_facecrop_boxes_f32'] = [_c_f32p, _i, _ip, _ip, ctypes.c_void_p]
 SIGNATURES['sgdfr_facecrop_forward_u8'] = [_u8p, _c_f32p, _i, _i, _i, _i, _i, _u8p, _ip, _c_f32p, _ip, _ip, _c_f32p, ctypes.c_void_p, _i64,
                                            ctypes.c_void_p]
-E4E_PARAMS_256 = 423    # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
+SIGNATURES['sgdfr_pairloss_forward_f32'] = [_c_f32p, _c_f32p, _i64, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+SIGNATURES['sgdfr_pairloss_backward_f32'] = [_c_f32p, _c_f32p, _i64, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]
+PAIRLOSS_PLAIN, PAIRLOSS_RANGE255 = 0, 1    # include/sgdfr.h SGDFR_PAIRLOSS_*
+E4E_PARAMS_256 = 423   # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
 OPTIONAL_SIGNATURES = {'sgdfr_mfma_ceiling_probe': [_i, _i, _i, _i, _i, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]}
@@ -228,6 +231,7 @@ SIZE_QUERIES = {
     'sgdfr_s3fd_pack_elems': 0, 'sgdfr_s3fd_debug_elems': 3, 'sgdfr_s3fd_map_elems': 3, 'sgdfr_s3fd_workspace_bytes': 3,
     'sgdfr_e4e_pack_elems': 1, 'sgdfr_e4e_debug_elems': 2, 'sgdfr_e4e_workspace_bytes': 2,
     'sgdfr_facecrop_workspace_bytes': 4,
+    'sgdfr_pairloss_workspace_bytes': 1,
 }
 COUNT_QUERIES = ('sgdfr_e4e_style_count', 'sgdfr_e4e_param_count')      # int (int R): a count, or -1 for a resolution out of range
 

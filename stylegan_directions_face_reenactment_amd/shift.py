@@ -155,6 +155,12 @@ class ShiftVectors:
         """utils_train.py:127-175: [B, learned_directions] in float32 tensor arithmetic."""
         return self._launch(self._table_train, 1, angles_source, angles_target, param_source, param_target)
 
+    def make_shifts_interpolation(self, param_source, param_target, angles_source, angles_target):
+        """utils_train.py:530-575, the shift vector of the validation pairs (evaluate_model_reenactment): make_shift_vector
+        operation for operation -- the same direction rows, the same float32 arithmetic -- so it is that launch.  The reference
+        sizes its output by test_batch_size; here it has one row per row of the arguments."""
+        return self.make_shift_vector(param_source, param_target, angles_source, angles_target)
+
     def make_shift_vector_50(self, param_source, param_target, angles_source, angles_target, target_indices=None, u=None,
                              indices_on_host=False):
         """utils_train.py:177-288: first half of the batch = full reenactment shift, second half = one random direction
