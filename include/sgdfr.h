@@ -34,6 +34,9 @@
  *                              libs/DECA/decalib/utils/rotation_converter.py:306-307
  *   sgdfr_pairloss_forward_f32 / _backward_f32  libs/utilities/utils_train.py:435-499 calculate_losses_paired: torch_range_1_to_255
  *                              (libs/utilities/image_utils.py:87-94), the pixel-wise L1 and the latent L1 regulariser
+ *   sgdfr_sweep_plan_f32 / _rows_f32  libs/configs/config_directions.py:42-85 get_direction_info and the np.arange / one_hot loops of
+ *                              run_facial_editing.py:172-189 and libs/utilities/visualization.py:46-60, for all ladders at once
+ *   sgdfr_sweep_frames_f32     face_pool (AdaptiveAvgPool2d), add_border, tensor_to_image + astype(uint8) of the same scripts
  */
 #ifndef SGDFR_H
 #define SGDFR_H
@@ -477,6 +480,65 @@ int sgdfr_pairloss_forward_f32(const float* x, const float* y, int64_t n, int mo
                                void* workspace, int64_t workspace_bytes, void* stream);
 int sgdfr_pairloss_backward_f32(const float* x, const float* y, int64_t n, int mode, const float* grad_loss,
                                 const float* grad_x255, float* dx, void* stream);
+
+/* ---- direction sweeps (run_facial_editing.py:144-207 interpolate, libs/utilities/visualization.py:13-73), csrc/sweep.hip ---- */
+
+/* One ladder: what libs/configs/config_directions.py:42-85 get_direction_info returns for one source along one direction, and the
+ * lengths of the two loops that walk it: n_lo = len(np.arange(min_shift, start, step)), n_hi = len(np.arange(start, max_shift, step)).
+ * start / min_shift / max_shift hold the reference's values exactly (float64 on angle directions, float32 widened on the others). */
+struct sgdfr_sweep_record {
+    double start;
+    double min_shift;
+    double max_shift;
+    double step;
+    int n_lo;
+    int n_hi;
+};
+
+/* get_direction_info for N source rows x K requested directions in one launch: records[n * K + j] describes source row n along
+ * direction dirs[j] (`dirs`, like `table`, is a HOST array; table as sgdfr_make_shift_f32 takes it, built the way the trainer's is:
+ * per-dataset angle rows, the jaw at count_pose - 1).  angles [N,3], pose [N,pose_dim], alpha_exp [N,exp_dim] and records are
+ * device arrays.  step = shift_scale / shifts_count.  The arithmetic reproduces the reference's mixed dtypes operation by operation
+ * (one rounding each, no fma):
+ *   SGDFR_DIR_ANGLE: start = (double)fl32(angle * fl32(shift_scale)) / b; min = -sc - start, max = (sc - start) + 1e-5 and both
+ *     length quotients ceil((stop - first) / step) in float64;
+ *   SGDFR_DIR_JAW / SGDFR_DIR_EXP: start = fl32(fl32(a) * x) + fl32(b) in float32; min, max and the quotients in float32 with sc, 1e-5
+ *     and step rounded to float32 first (NumPy >= 2 weak scalars against a 0-d float32 array).
+ * A requested direction of kind SGDFR_DIR_ZERO (absent from the dataset) is refused before the launch.
+ * sgdfr_sweep_plan_host runs the same per-ladder function over HOST arrays: no GPU is touched. */
+int sgdfr_sweep_plan_f32(const float* angles, const float* pose, const float* alpha_exp, int pose_dim, int exp_dim,
+                         const struct sgdfr_direction* table, int D, const int* dirs, int K, double shift_scale, int shifts_count,
+                         struct sgdfr_sweep_record* records, int N, void* stream);
+int sgdfr_sweep_plan_host(const float* angles, const float* pose, const float* alpha_exp, int pose_dim, int exp_dim,
+                          const struct sgdfr_direction* table, int D, const int* dirs, int K, double shift_scale, int shifts_count,
+                          struct sgdfr_sweep_record* records, int N);
+
+/* The ladders as DirectionMatrix input: rows [R,D] float32, row r = one_hot(D, value, dirs[j]) (libs/utilities/utils.py:62-65), every
+ * other column exactly 0.  Pair p = n * K + j owns rows row_offset[p] .. row_offset[p] + n_lo + n_hi - 1 (row_offset: device int32
+ * [N*K], the exclusive prefix sum of the lengths): first np.arange(min_shift, start, step) ascending, then
+ * np.arange(start, max_shift, step) ascending.  value_i = first + i * delta in float64, rounded to float32 once, with
+ * delta = (first + step) - first in float64 on angle directions and (double)fl32(first + fl32(step)) - first on the others.
+ * row_k[r] = j (the position in dirs), is_start[r] = 1 on the first row of the second part (the row interpolate draws the red box
+ * on), both device int32 [R].  A row that the offsets do not cover is left zero with row_k = -1.
+ * sgdfr_sweep_rows_host does the same over HOST arrays (rows in pair order, R must equal the records' total). */
+int sgdfr_sweep_rows_f32(const struct sgdfr_sweep_record* records, const int* row_offset, const struct sgdfr_direction* table, int D,
+                         const int* dirs, int K, int N, float* rows, int* row_k, int* is_start, int R, void* stream);
+int sgdfr_sweep_rows_host(const struct sgdfr_sweep_record* records, const struct sgdfr_direction* table, int D, const int* dirs, int K,
+                          int N, float* rows, int* row_k, int* is_start, int64_t R);
+
+/* Rendered rows -> what the editing scripts consume, in one pass: x [R,3,P*f,P*f] float32, f = 1, 2 or 4.  Outputs, each skipped when
+ * NULL:
+ *   pooled   [R,3,P,P] float32: the f x f mean, summed row by row and left to right, divided by f*f last
+ *            (AdaptiveAvgPool2d((P,P)) for these factors);
+ *   bordered [R,3,P,P] float32: pooled with add_border (libs/utilities/image_utils.py:129-137: 3 pixels, R = 1, G = B = -1) on the
+ *            rows whose is_start flag (device int32 [R]) is set; needs P >= 7;
+ *   frames   [R,P,panels*P,3] uint8: tensor_to_image(...).astype(uint8) of the pooled value (the arithmetic of
+ *            sgdfr_image_to_u8_f32), never bordered; panels = 2 puts src [R or 1,3,P,P] (src_bstride = 3*P*P or 0) in the left
+ *            panel (run_facial_editing.py:198-203).
+ * 16-byte loads when P*f is a multiple of 4 and x is 16-byte aligned, dword loads of the same elements in the same order otherwise:
+ * the results do not depend on the path.  No atomics, no LDS. */
+int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const int* is_start, const float* src, int64_t src_bstride,
+                           float* pooled, float* bordered, unsigned char* frames, int panels, void* stream);
 
 /* ---- backward helpers (autograd of model.py:232-359 as restated in SURVEY.md Appendix C) ------------------------ */
 

@@ -215,6 +215,23 @@ SIGNATURES['sgdfr_facecrop_forward_u8'] = [_u8p, _c_f32p, _i, _i, _i, _i, _i, _u
 SIGNATURES['sgdfr_pairloss_forward_f32'] = [_c_f32p, _c_f32p, _i64, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
 SIGNATURES['sgdfr_pairloss_backward_f32'] = [_c_f32p, _c_f32p, _i64, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]
 PAIRLOSS_PLAIN, PAIRLOSS_RANGE255 = 0, 1    # include/sgdfr.h SGDFR_PAIRLOSS_*
+
+
+class SweepRecord(ctypes.Structure):
+    """struct sgdfr_sweep_record (include/sgdfr.h)."""
+    _fields_ = [('start', ctypes.c_double), ('min_shift', ctypes.c_double), ('max_shift', ctypes.c_double), ('step', ctypes.c_double),
+                ('n_lo', ctypes.c_int), ('n_hi', ctypes.c_int)]
+
+
+_host_ip = ctypes.POINTER(ctypes.c_int)  # int* on the HOST
+SIGNATURES['sgdfr_sweep_plan_f32'] = [_c_f32p, _c_f32p, _c_f32p, _i, _i, ctypes.POINTER(Direction), _i, _host_ip, _i, ctypes.c_double, _i,
+                                      ctypes.c_void_p, _i, ctypes.c_void_p]
+SIGNATURES['sgdfr_sweep_plan_host'] = [_c_f32p, _c_f32p, _c_f32p, _i, _i, ctypes.POINTER(Direction), _i, _host_ip, _i, ctypes.c_double, _i,
+                                       ctypes.c_void_p, _i]
+SIGNATURES['sgdfr_sweep_rows_f32'] = [ctypes.c_void_p, _ip, ctypes.POINTER(Direction), _i, _host_ip, _i, _i, _c_f32p, _ip, _ip, _i,
+                                      ctypes.c_void_p]
+SIGNATURES['sgdfr_sweep_rows_host'] = [ctypes.c_void_p, ctypes.POINTER(Direction), _i, _host_ip, _i, _i, _c_f32p, _ip, _ip, _i64]
+SIGNATURES['sgdfr_sweep_frames_f32'] = [_c_f32p, _i, _i, _i, _ip, _c_f32p, _i64, _c_f32p, _c_f32p, _u8p, _i, ctypes.c_void_p]
 E4E_PARAMS_256 = 423   # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)

@@ -12,7 +12,8 @@ download); ``install_id_loss(path)`` (opt-in) mounts the HIP identity loss at ``
 unchanged ``SFDDetector(device, path)`` (landmarks_estimation.py:118) gets it.  ``install_face_crop()`` (opt-in) mounts the HIP
 alignment crop at ``libs.face_models.ffhq_cropping`` (numpy in, numpy out, as preprocess_image calls it).  There is no ``install_landmarks``:
 ``LandmarksEstimation`` crops and runs one face at a time around the FAN network; call ``face_detector.detect_landmarks`` or
-``landmarks.get_landmarks`` instead.  ``libs.utilities.generic`` is NOT replaced wholesale
+``landmarks.get_landmarks`` instead.  ``install_visualization()`` (opt-in) mounts the batched direction sweep's ``make_interpolation_chart`` at
+``libs.utilities.visualization``.  ``libs.utilities.generic`` is NOT replaced wholesale
 (it also holds DECA glue); call ``patch_generic(module)`` to swap in the two fused functions.
 """
 import importlib
@@ -172,3 +173,58 @@ def install_face_crop():
     mod.__doc__ = 'HIP alignment crop mounted by stylegan_directions_face_reenactment_amd.compat.install_face_crop'
     _mount(FACE_CROP_ALIAS, mod)
     return FACE_CROP_ALIAS
+
+
+VISUALIZATION_ALIAS = 'libs.utilities.visualization'
+_visualization_saved = []
+
+
+def install_visualization():
+    """Mount a module at libs.utilities.visualization whose make_interpolation_chart is the batched sweep (sweep.py) with the
+    reference's signature and return value, and whose get_shifted_image is the reference's single frame -- so an unchanged
+    `from libs.utilities.visualization import make_interpolation_chart` (utils_train.py:653-691 log_interpolation) gets it.  Opt-in:
+    install() does not call it.  uninstall_visualization() puts back whatever was mounted there before.  Parent packages that cannot
+    be imported are created empty."""
+    from . import generic, sweep
+    parts = VISUALIZATION_ALIAS.split('.')
+    before = set(sys.modules)
+    _parent_packages(VISUALIZATION_ALIAS)
+    created = [n for n in ('.'.join(parts[:i]) for i in range(1, len(parts))) if n not in before]
+    parent, _, leaf = VISUALIZATION_ALIAS.rpartition('.')
+    _visualization_saved.append((sys.modules.get(VISUALIZATION_ALIAS), getattr(sys.modules[parent], leaf, None), created))
+
+    def get_shifted_image(G, A_matrix, source_code, shift, direction_index, truncation, trunc, w_plus, input_is_latent, num_layers_shift):
+        import torch
+        shift_vector = torch.zeros(A_matrix.input_dim)
+        shift_vector[direction_index] = shift                            # utils.py:62-65 one_hot
+        return generic.generate_image(G, source_code, truncation, trunc, w_plus, shift_code=A_matrix(shift_vector.cuda()),
+                                      input_is_latent=input_is_latent, num_layers_shift=num_layers_shift)
+
+    mod = types.ModuleType(VISUALIZATION_ALIAS)
+    mod.make_interpolation_chart = sweep.make_interpolation_chart
+    mod.get_shifted_image = get_shifted_image
+    mod.__doc__ = 'HIP direction sweeps mounted by stylegan_directions_face_reenactment_amd.compat.install_visualization'
+    _mount(VISUALIZATION_ALIAS, mod)
+    return VISUALIZATION_ALIAS
+
+
+def uninstall_visualization():
+    """Undo the last install_visualization(): the module and the parent's attribute as they were before it (absent if they were),
+    and the parent packages it had to create."""
+    if not _visualization_saved:
+        return False
+    old_mod, old_attr, created = _visualization_saved.pop()
+    parent, _, leaf = VISUALIZATION_ALIAS.rpartition('.')
+    if old_mod is None:
+        sys.modules.pop(VISUALIZATION_ALIAS, None)
+    else:
+        sys.modules[VISUALIZATION_ALIAS] = old_mod
+    if parent in sys.modules:
+        if old_attr is None:
+            if hasattr(sys.modules[parent], leaf):
+                delattr(sys.modules[parent], leaf)
+        else:
+            setattr(sys.modules[parent], leaf, old_attr)
+    for name in created:
+        sys.modules.pop(name, None)
+    return True
