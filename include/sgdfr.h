@@ -37,6 +37,7 @@
  *   sgdfr_sweep_plan_f32 / _rows_f32  libs/configs/config_directions.py:42-85 get_direction_info and the np.arange / one_hot loops of
  *                              run_facial_editing.py:172-189 and libs/utilities/visualization.py:46-60, for all ladders at once
  *   sgdfr_sweep_frames_f32     face_pool (AdaptiveAvgPool2d), add_border, tensor_to_image + astype(uint8) of the same scripts
+ *   sgdfr_video_frames_f32     face_pool + generate_grid_image + tensor_to_image + np.uint8 + cvtColor of run_inference.py:180-195
  */
 #ifndef SGDFR_H
 #define SGDFR_H
@@ -539,6 +540,17 @@ int sgdfr_sweep_rows_host(const struct sgdfr_sweep_record* records, const struct
  * the results do not depend on the path.  No atomics, no LDS. */
 int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const int* is_start, const float* src, int64_t src_bstride,
                            float* pooled, float* bordered, unsigned char* frames, int panels, void* stream);
+
+/* Rendered rows -> grid video frames in one pass (the frames of a session that pools, reenact.ReenactmentSession(pool_to=...)):
+ * x [B,3,P*f,P*f] float32, f = 1, 2 or 4 -> frames [B,P,(n_left+1)*P,3] uint8.  Panels 0 .. n_left-1 (n_left <= 3) are
+ * `panels[k]` [B or 1,3,P,P] float32 with batch stride `bstrides[k]` (3*P*P, or 0 = the same image in every frame); both are HOST
+ * arrays, as sgdfr_grid_to_u8_f32 takes them, and a NULL panel leaves its columns of `frames` as they are.  The last panel is the
+ * f x f mean of x in sgdfr_sweep_frames_f32's arithmetic (summed row by row and left to right, divided by f*f last).  Every byte is
+ * sgdfr_image_to_u8_f32's; swap_rb != 0 stores the channels in reverse order in every panel, as sgdfr_grid_to_u8_f32 does.  The
+ * bytes equal sgdfr_sweep_frames_f32(pooled) followed by sgdfr_grid_to_u8_f32 without the float intermediate.  16-byte loads of x
+ * when P*f is a multiple of 4 and x is 16-byte aligned, dword loads of the same elements otherwise; byte stores.  No atomics, no LDS. */
+int sgdfr_video_frames_f32(const float* x, int B, int P, int f, const float* const* panels, const int64_t* bstrides, int n_left,
+                           unsigned char* frames, int swap_rb, void* stream);
 
 /* ---- backward helpers (autograd of model.py:232-359 as restated in SURVEY.md Appendix C) ------------------------ */
 

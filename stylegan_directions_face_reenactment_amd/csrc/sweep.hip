@@ -7,6 +7,7 @@
 //   sweep_plan    one thread per (source row, direction): start / min / max / step and the two arange lengths, on the device
 //   sweep_rows    one thread per ladder row: the [R, D] one-hot matrix, the row -> direction map and the `start` flag
 //   sweep_frames  one pass over the rendered rows: f x f mean, red border on the start rows, uint8 gif frames
+//   video_frames  the same pass for the reenactment video: f x f mean next to up to three left panels, uint8 grid frames
 //
 // The ladder arithmetic mirrors the reference's mixed NumPy / torch dtypes operation by operation -- the lengths depend on it:
 //   angle directions   a 0-d float32 array times a Python number is float32, the division by the float64 angle scale and everything
@@ -246,6 +247,93 @@ __global__ __launch_bounds__(256) void sweep_frames_scalar_kernel(const float* _
     }
 }
 
+// ---------------------------------------------------------------- video frames (pooled sessions)
+// rendered rows -> [B,P,K*P,3] uint8 grid frames in one pass: up to three left panels [B or 1,3,P,P] converted as
+// grid_to_u8_kernel converts them, the f x f mean of x (the arithmetic of the frames kernels above) in the last panel.
+constexpr int kVideoLeft = 3;
+
+struct VideoPanels {
+    const float* x[kVideoLeft];
+    int64_t bstride[kVideoLeft];
+    int n;                                             // left panels; the pooled rows go into panel n
+};
+
+// one output pixel (b, oy, ox) of every panel.  Byte stores: a panel starts at a multiple of P*3 bytes, which is not a multiple of 4
+// for every P (P = 7), and adjacent lanes write adjacent 3-byte pixels, so the stores of a wave still fill whole lines.
+__device__ __forceinline__ void put_video_pixel(const VideoPanels& g, unsigned char* __restrict__ frames, int b, int oy, int ox, int P,
+                                                int swap_rb, const float (&v)[3]) {
+    const int64_t PP = (int64_t)P * P;
+    unsigned char* line = frames + ((int64_t)b * P + oy) * (int64_t)(g.n + 1) * P * 3 + (int64_t)ox * 3;
+#pragma unroll
+    for (int k = 0; k < kVideoLeft; ++k) {
+        if (k >= g.n) break;
+        if (g.x[k]) {
+            const float* s = g.x[k] + (int64_t)b * g.bstride[k] + (int64_t)oy * P + ox;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) line[swap_rb ? 2 - c : c] = to_u8(s[c * PP]);
+        }
+        line += (int64_t)P * 3;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) line[swap_rb ? 2 - c : c] = to_u8(v[c]);
+}
+
+// the lane scheme of sweep_frames_vec_kernel: four consecutive input columns of F rows per lane, 16-byte loads
+template <int F>
+__global__ __launch_bounds__(256) void video_frames_vec_kernel(const float* __restrict__ x, VideoPanels g,
+                                                               unsigned char* __restrict__ frames, int B, int P, int swap_rb) {
+    constexpr int NPIX = 4 / F;
+    const int W = P * F, Q = W / 4;
+    const int64_t items = (int64_t)B * P * Q, plane = (int64_t)W * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % Q);
+        const int64_t t = i / Q;
+        const int oy = (int)(t % P), b = (int)(t / P);
+        float acc[3][NPIX];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int p = 0; p < NPIX; ++p) acc[c][p] = 0.f;
+            const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * F * W + (int64_t)q * 4;
+#pragma unroll
+            for (int dy = 0; dy < F; ++dy) {
+                const float4 v = *reinterpret_cast<const float4*>(xp + (int64_t)dy * W);
+                const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[c][j / F] += e[j];
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < NPIX; ++p) {
+            const float v[3] = {acc[0][p] / (float)(F * F), acc[1][p] / (float)(F * F), acc[2][p] / (float)(F * F)};
+            put_video_pixel(g, frames, b, oy, q * NPIX + p, P, swap_rb, v);
+        }
+    }
+}
+
+// dword path: one output pixel per lane, the same order of additions
+__global__ __launch_bounds__(256) void video_frames_scalar_kernel(const float* __restrict__ x, VideoPanels g,
+                                                                  unsigned char* __restrict__ frames, int B, int P, int f, int swap_rb) {
+    const int W = P * f;
+    const int64_t items = (int64_t)B * P * P, plane = (int64_t)W * W;
+    const float ff = (float)(f * f);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(i % P);
+        const int64_t t = i / P;
+        const int oy = (int)(t % P), b = (int)(t / P);
+        float v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * f * W + (int64_t)ox * f;
+            float s = 0.f;
+            for (int dy = 0; dy < f; ++dy)
+                for (int dx = 0; dx < f; ++dx) s += xp[(int64_t)dy * W + dx];
+            v[c] = s / ff;
+        }
+        put_video_pixel(g, frames, b, oy, ox, P, swap_rb, v);
+    }
+}
+
 static int gather_table(const char* who, const sgdfr_direction* table, int D, const int* dirs, int K, int pose_dim, int exp_dim,
                         SweepTable* out) {
     SGDFR_REQUIRE(table && D >= 1 && D <= SGDFR_MAX_DIRECTIONS, "%s: 1..%d directions, got %d", who, SGDFR_MAX_DIRECTIONS, D);
@@ -367,4 +455,33 @@ extern "C" int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const
     else if (f == 2) hipLaunchKernelGGL(sweep_frames_vec_kernel<2>, grid, block, 0, st, x, o, R, P);
     else hipLaunchKernelGGL(sweep_frames_vec_kernel<4>, grid, block, 0, st, x, o, R, P);
     return check_launch("sweep_frames");
+}
+
+extern "C" int sgdfr_video_frames_f32(const float* x, int B, int P, int f, const float* const* panels, const int64_t* bstrides, int n_left,
+                                      unsigned char* frames, int swap_rb, void* stream) {
+    SGDFR_REQUIRE(f == 1 || f == 2 || f == 4, "video_frames: the pooling factor must be 1, 2 or 4 (256, 512, 1024 generators), got %d", f);
+    SGDFR_REQUIRE(B >= 0 && P >= 1 && P <= 8192, "video_frames: bad shape B=%d P=%d", B, P);
+    SGDFR_REQUIRE(n_left >= 0 && n_left <= kVideoLeft, "video_frames: %d left panels (0..%d)", n_left, kVideoLeft);
+    SGDFR_REQUIRE(n_left == 0 || (panels && bstrides), "video_frames: left panels without their pointer and stride arrays");
+    VideoPanels g{};
+    g.n = n_left;
+    for (int k = 0; k < n_left; ++k) {
+        SGDFR_REQUIRE(bstrides[k] == 0 || bstrides[k] == (int64_t)3 * P * P, "video_frames: panel %d is one image (stride 0) or one per row", k);
+        g.x[k] = panels[k];
+        g.bstride[k] = bstrides[k];
+    }
+    if (B == 0) return 0;
+    SGDFR_REQUIRE(x && frames, "video_frames: null pointer");
+    const int W = P * f;
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    const int64_t items = vec ? (int64_t)B * P * (W / 4) : (int64_t)B * P * P;
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    const dim3 grid((unsigned)blocks), block(256);
+    hipStream_t st = as_stream(stream);
+    if (!vec) hipLaunchKernelGGL(video_frames_scalar_kernel, grid, block, 0, st, x, g, frames, B, P, f, swap_rb);
+    else if (f == 1) hipLaunchKernelGGL(video_frames_vec_kernel<1>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    else if (f == 2) hipLaunchKernelGGL(video_frames_vec_kernel<2>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    else hipLaunchKernelGGL(video_frames_vec_kernel<4>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    return check_launch("video_frames");
 }

@@ -8,6 +8,10 @@ Every frame depends only on the fixed source code and its own shift vector, so N
 batch.  `ReenactmentSession.frames` chunks the shift vectors, broadcasts the source W+ code inside
 ``sgdfr_latent_prepare_f32`` (shift add + truncation in the same launch) and yields [b,3,H,W] images, optionally
 converted on the GPU to the uint8 HWC layout the reference writes (libs/utilities/image_utils.py:97-110).
+
+`Reenactor` is the caller above it: Inference.run_reenactment whole (run_inference.py:157-199), target frames in, video frames out
+-- the source side once (`set_source`: crop, e4e, PTI on a copy of G, the source's 3DMM parameters), then per batch of target frames
+S3FD, FAN, the alignment crop, DECA, the shift vectors, a stated policy for frames that fail, and the session.
 """
 import ctypes
 import os
@@ -68,6 +72,86 @@ def grid_frames_uint8(panels, swap_rb=False, out=None):
         raise RuntimeError('grid_frames_uint8: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (B, H, K * W))
     N.call('sgdfr_grid_to_u8_f32', ptrs, strides, K, N.ptr(out), B, H, W, int(bool(swap_rb)), N.stream())
     return out
+
+
+def _pool_factor(size, pool_to):
+    """f = size / pool_to for the pooled outputs (1, 2 or 4: what the frames kernels take)."""
+    f = size // pool_to if isinstance(pool_to, int) and not isinstance(pool_to, bool) and pool_to > 0 and size % pool_to == 0 else 0
+    if f not in (1, 2, 4):
+        raise RuntimeError('pool_to must be None or a divisor of the generator size %d that leaves a factor of 1, 2 or 4, got %r'
+                           % (size, pool_to))
+    return f
+
+
+def pool_images(x, P, as_uint8=False):
+    """x [B,3,P*f,P*f] float32 -> the f x f mean [B,3,P,P] float32, or with as_uint8 its [B,P,P,3] uint8 frames: one
+    ``sgdfr_sweep_frames_f32`` launch (AdaptiveAvgPool2d((P,P)) for f = 1, 2, 4, as generic.generate_image pools above 256)."""
+    N.require_device(x)
+    x = N.f32c(x)
+    if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise RuntimeError('pool_images: expected square RGB images [B,3,S,S], got %s' % (tuple(x.shape),))
+    B, f = x.shape[0], _pool_factor(x.shape[2], P)
+    y = torch.empty((B, P, P, 3) if as_uint8 else (B, 3, P, P), device=x.device, dtype=torch.uint8 if as_uint8 else torch.float32)
+    N.call('sgdfr_sweep_frames_f32', N.ptr(x), B, P, f, None, None, 0, None if as_uint8 else N.ptr(y), None,
+           N.ptr(y) if as_uint8 else None, 1, N.stream())
+    return y
+
+
+def video_frames_uint8(x, panels=(), P=None, swap_rb=False, out=None):
+    """Rendered rows to grid frames in ONE launch (``sgdfr_video_frames_f32``): x [B,3,P*f,P*f] float32 (f = 1, 2 or 4; P defaults to
+    256, or the side of x below that) is pooled f x f and placed to the right of up to three left `panels` ([B or 1,3,P,P] float32;
+    None = leave that panel of `out` as it is) -> [B,P,K*P,3] uint8, K = len(panels) + 1.  The bytes are those of
+    pool_images(x, P) -> grid_frames_uint8(panels + [pooled]) without the float intermediate."""
+    N.require_device(x)
+    x = N.f32c(x)
+    if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise RuntimeError('video_frames_uint8: expected square RGB images [B,3,S,S], got %s' % (tuple(x.shape),))
+    B, S = x.shape[0], x.shape[2]
+    if P is None:
+        P = min(S, 256)
+    f = _pool_factor(S, P)
+    if len(panels) > 3:
+        raise RuntimeError('video_frames_uint8 takes up to 3 left panels, got %d' % len(panels))
+    xs = []
+    for p in panels:
+        if p is None:
+            xs.append(None)
+            continue
+        N.require_device(p)
+        p = N.f32c(p if p.ndim == 4 else p.unsqueeze(0))
+        if tuple(p.shape[1:]) != (3, P, P) or p.shape[0] not in (1, B):
+            raise RuntimeError('video_frames_uint8: left panels must be [1 or %d,3,%d,%d], got %s' % (B, P, P, tuple(p.shape)))
+        xs.append(p)
+    K = len(xs) + 1
+    if out is None:
+        if any(p is None for p in xs):
+            raise RuntimeError('video_frames_uint8: a skipped panel needs the `out` tensor that already holds it')
+        out = torch.empty(B, P, K * P, 3, device=x.device, dtype=torch.uint8)
+    elif tuple(out.shape) != (B, P, K * P, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+        raise RuntimeError('video_frames_uint8: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (B, P, K * P))
+    n = max(len(xs), 1)
+    ptrs = (ctypes.c_void_p * n)(*[None if p is None else p.data_ptr() for p in xs])
+    strides = (ctypes.c_int64 * n)(*[0 if (p is None or (p.shape[0] == 1 and B > 1)) else 3 * P * P for p in xs])
+    N.call('sgdfr_video_frames_f32', N.ptr(x), B, P, f, ptrs, strides, len(xs), N.ptr(out), int(bool(swap_rb)), N.stream())
+    return out
+
+
+def hold_failed_rows(sv, ok, carry, carry_valid):
+    """The 'hold' policy for target frames that failed: every row of sv [N,D] whose `ok` [N] (bool) is False takes the vector of the
+    nearest earlier ok row; before the first ok row it takes `carry` [D] when `carry_valid` (0-d bool tensor) is set -- the last good
+    vector of the calls before this one -- and zeros otherwise (a zero shift vector renders the inverted source).  Rows that are ok
+    pass through bit for bit, whatever the failed rows hold (NaNs included).  Returns (sv, carry, carry_valid) with the carry for
+    the next call.  Plain torch on the tensors' device (CPU tensors too), no host read."""
+    n = sv.shape[0]
+    if n == 0:
+        return sv, carry, carry_valid
+    ok = ok.to(torch.bool)
+    idx = torch.arange(n, device=sv.device)
+    last = torch.cummax(torch.where(ok, idx, torch.full_like(idx, -1)), 0).values        # nearest ok row at or before each row, or -1
+    before = torch.where(carry_valid, carry, torch.zeros_like(carry)).to(sv.dtype)
+    held = torch.where((last >= 0).unsqueeze(1), sv.index_select(0, last.clamp(min=0)), before.unsqueeze(0))
+    out = torch.where(ok.unsqueeze(1), sv, held)
+    return out, out[-1].clone(), carry_valid | ok.any()
 
 
 def save_latent_codes(directory, names, latents):
@@ -134,7 +218,7 @@ def load_latent_codes(paths, device=None):
 class ReenactmentSession:
     """One source identity, many target poses/expressions."""
 
-    def __init__(self, G, A, source_code, truncation=0.7, trunc=None, batch=32, graph=False, shifts=None, streams=2):
+    def __init__(self, G, A, source_code, truncation=0.7, trunc=None, batch=32, graph=False, shifts=None, streams=2, pool_to=None):
         """shifts: a `shift.ShiftVectors` (direction tables of the dataset) -- then `render_targets` / `frames_for_targets`
         take the 3DMM parameters of source and targets and build the shift vectors on the device too.
         graph=True captures one `batch`-sized step (DirectionMatrix -> shift -> generator) in a hipGraph the first time a
@@ -143,7 +227,16 @@ class ReenactmentSession:
         (call `reset_graph()` after loading new ones); partial last batches run eagerly.
         streams: consecutive chunks alternate between this many HIP streams (functional.StreamPipeline: the latency-bound head
         of chunk i+1 runs beside the big layers of chunk i; 1 = everything on the caller's stream).  Replayed graphs share
-        their static buffers and stay on the caller's stream."""
+        their static buffers and stay on the caller's stream.
+        pool_to: the side P of what the session hands back for a generator above it (256 for the 512 and 1024 generators): `frames`,
+        `render` and `streaming` give images pooled f x f as generic.generate_image pools them (generic.py:51-52; here the frames
+        kernel's mean, pool_images), `video_frames` writes the pooled reenacted panel (video_frames_uint8).  The last ToRGB
+        launch's direct uint8 write (functional.U8Target) is bypassed on this path: it has full-size pixels to offer.  None (the
+        default): images of the generator's own size, as before."""
+        self.pool_to, self.pool_f = None, 1
+        if pool_to is not None:
+            self.pool_f = _pool_factor(G.size, pool_to)
+            self.pool_to = int(pool_to) if self.pool_f > 1 else None
         if source_code.ndim == 2:
             source_code = source_code.unsqueeze(0)
         if source_code.shape[0] != 1 or source_code.shape[1] != G.n_latent:
@@ -273,13 +366,15 @@ class ReenactmentSession:
 
             def _out(self, item):
                 lo, sv, u8, img, graphed = self.chunks.settle(item)
+                if sess.pool_to is not None:
+                    return pool_images(img, sess.pool_to, as_uint8)
                 return images_to_uint8(img) if (as_uint8 and graphed) else img
 
             @torch.no_grad()
             def push(self, shift_vectors):
                 if self.chunks is None:
                     self.chunks = sess._chunks(True, shift_vectors.device)
-                cur = self.chunks.launch(self.count, shift_vectors, F_.U8Target() if as_uint8 else None)
+                cur = self.chunks.launch(self.count, shift_vectors, F_.U8Target() if (as_uint8 and sess.pool_to is None) else None)
                 self.count += shift_vectors.shape[0]
                 prev, self.pending = self.pending, cur
                 return self._out(prev) if prev is not None else None
@@ -294,6 +389,10 @@ class ReenactmentSession:
     @torch.no_grad()
     def frames(self, shift_vectors, as_uint8=False):
         """shift_vectors [N, input_dim] -> generator of image batches (same result as N generate_image calls)."""
+        if self.pool_to is not None:
+            for lo, sv, u8, img, graphed in self._pipeline(shift_vectors, None):
+                yield pool_images(img, self.pool_to, as_uint8)
+            return
         for lo, sv, u8, img, graphed in self._pipeline(shift_vectors, (lambda lo, b: F_.U8Target()) if as_uint8 else None):
             # eager uint8 frames come straight out of the last ToRGB launch (no fp32 image is stored); a replayed graph
             # produced fp32 images
@@ -323,9 +422,175 @@ class ReenactmentSession:
         n = shift_vectors.shape[0]
         H, W = source_image.shape[-2], source_image.shape[-1]
         video = torch.empty(n, H, 3 * W, 3, device=shift_vectors.device, dtype=torch.uint8)
+        if self.pool_to is not None:
+            if (H, W) != (self.pool_to, self.pool_to):
+                raise RuntimeError('video_frames: this session pools to %d, the source panel is %d x %d' % (self.pool_to, H, W))
+            for lo, sv, u8, img, graphed in self._pipeline(shift_vectors, None):
+                b = sv.shape[0]
+                video_frames_uint8(img, [source_image, target_images[lo:lo + b]], self.pool_to, swap_rb=swap_rb, out=video[lo:lo + b])
+            return video
         # eager chunks: the reenacted panel is written by the generator's last launch; the other two by one grid launch
         target_for = lambda lo, b: F_.U8Target(video[lo:lo + b], panel=2, swap_rb=swap_rb)
         for lo, sv, u8, img, graphed in self._pipeline(shift_vectors, target_for):
             frames = video[lo:lo + sv.shape[0]]
             grid_frames_uint8([source_image, target_images[lo:lo + sv.shape[0]], img if graphed else None], swap_rb=swap_rb, out=frames)
         return video
+
+
+ON_FAIL = ('hold', 'source', 'raise')
+OUTPUTS = ('video', 'images')
+
+
+def _device_frames(frames, who):
+    if not torch.is_tensor(frames):
+        raise RuntimeError('%s: expected a uint8 tensor of frames, got %s' % (who, type(frames)))
+    N.require_device(frames, dtype=torch.uint8)
+    return frames
+
+
+class Reenactor:
+    """Frames in, video frames out: Inference.run_reenactment of the reference (run_inference.py:157-199) on this package's heads.
+
+        r = Reenactor(G, A, enc, det, fan, E, shifts, truncation=0.7, trunc=trunc, lpips=lpips, batch=32)
+        info = r.set_source(frame)                        # crop -> e4e -> PTI on a copy of G -> session -> the source's 3DMM parameters
+        video, ok, sv = r.reenact(frames)                 # [N,256,768,3] uint8: source crop | target crop | reenacted
+
+    G / A: the generator and its DirectionMatrix; enc: the e4e encoder (encoder.encode); det, fan: S3FD and FAN; E: the DECA encoder;
+    shifts: the shift.ShiftVectors of the dataset; trunc: the truncation latent; lpips: the lpips.LPIPS of the PTI loss (needed for
+    set_source(optimize=True) only); batch: target frames per launch of every head and of the generator.  A generator above 256^2
+    is rendered through a session that pools to 256 (ReenactmentSession(pool_to=256)), as generic.generate_image does in the
+    reference's loop.  image_resize(width=1000) of the reference's preprocess_image stays with the caller.
+
+    Three deliberate deviations from the reference:
+      * a target frame that fails (no face on the frame, an invalid crop, no face on the crop, or the caller's `valid` mask) is
+        rendered by a stated policy (`on_fail`); the reference exits on the first two and renders from angles of -180 and zero
+        coefficients on the third (estimate_DECA.py:48-51);
+      * PTI uses the `trunc` given here; the reference's optimize_g draws a fresh mean_latent(4096) of its own (optimization.py:26);
+      * PTI tunes a deep copy: `G` stays bit-unchanged, so the next set_source starts from the base generator.  The reference's
+        optimize_g trains the generator it is handed (optimization.py:28-29 copies it for the regulariser only)."""
+
+    def __init__(self, G, A, enc, det, fan, E, shifts, truncation=0.7, trunc=None, lpips=None, batch=32):
+        if truncation < 1 and trunc is None:
+            raise RuntimeError('truncation < 1 needs the truncation latent')
+        if A.input_dim != shifts.learned_directions:
+            raise RuntimeError('Reenactor: the DirectionMatrix takes %d directions, the tables hold %d' % (A.input_dim, shifts.learned_directions))
+        self.G, self.A, self.enc, self.det, self.fan, self.E, self.shifts = G, A, enc, det, fan, E, shifts
+        self.truncation, self.trunc, self.lpips, self.batch = truncation, trunc, lpips, int(batch)
+        self.pool_to = 256 if G.size > 256 else None
+        self.session = None             # set_source makes these
+        self.G_source = self.source_x = self.source_params = self.source_angles = None
+        self._carry = self._carry_valid = None
+
+    def set_source(self, frame, optimize=True, opt_steps=200, lr=3e-3):
+        """load_source_data + run_inference.py:169 for one source frame [H,W,3] or [1,H,W,3] uint8 on the device:
+        preprocess_frames at B=1 -> invert_images -> (optimize) finetune.optimize_g with PtiLoss(lpips, x) on a deep copy of G,
+        optimize_all=False, the Reenactor's trunc -> a ReenactmentSession on the tuned copy (on G itself without optimisation,
+        run_inference.py:121-124) -> train_step.shape_params of the crop x (the cropped real image, not the inversion) -> the
+        hold carry of `reenact` is reset.  Returns {'crop' [1,256,256,3] uint8, 'x' [1,3,256,256], 'source_code', 'inverted',
+        'params', 'angles', 'loss': the last PTI loss as a 0-d device tensor (None without optimisation)}.
+
+        ONE host read of its own: the source's `ok` flag -- a source without a usable face raises RuntimeError (the reference exits
+        there).  Nothing else in this method's own code synchronises; the heads keep their own behaviour (a verified generator
+        forward waits for its range check)."""
+        from . import finetune
+        from .train_step import shape_params
+        if optimize and self.lpips is None:
+            raise RuntimeError('set_source(optimize=True) needs the LPIPS head of the PTI loss (Reenactor(..., lpips=...))')
+        frame = _device_frames(frame, 'set_source')
+        if frame.ndim == 3:
+            frame = frame.unsqueeze(0)
+        if frame.ndim != 4 or frame.shape[0] != 1:
+            raise RuntimeError('set_source: one source frame [H,W,3] or [1,H,W,3], got %s' % (tuple(frame.shape),))
+        if optimize and self.G.size != 256:
+            raise RuntimeError('set_source(optimize=True): PTI compares the generator output with the 256 x 256 crop; this generator '
+                               'renders %d x %d' % (self.G.size, self.G.size))
+        crop, x, ok = preprocess_frames(self.det, self.fan, frame.contiguous())
+        if not bool(ok.item()):                                            # the one host read
+            raise RuntimeError('set_source: no usable face in the source frame (no detection, or a crop outside the size limits)')
+        with torch.no_grad():
+            code, inverted = invert_images(self.enc, self.G, x, self.truncation, self.trunc)
+        G_source, loss = self.G, None
+        if optimize:
+            import copy
+            G_source = copy.deepcopy(self.G)                               # (model.Generator.__deepcopy__ leaves graphs and tokens behind)
+            G_source.invalidate_packs()                                    # ... and the copied weight packs are keyed on G's storage
+            G_source, loss = finetune.optimize_g(G_source, code, x, self.trunc, opt_steps=opt_steps, lr=lr, optimize_all=False,
+                                                 loss_fn=finetune.PtiLoss(self.lpips, x), truncation=self.truncation)
+            G_source.eval()
+            for p in G_source.parameters():
+                p.grad = None
+        self.G_source = G_source
+        self.session = ReenactmentSession(G_source, self.A, code, self.truncation, self.trunc, batch=self.batch, shifts=self.shifts,
+                                          pool_to=self.pool_to)
+        with torch.no_grad():
+            self.source_params, self.source_angles = shape_params(self.det, self.fan, self.E, x)
+        self.source_x = x
+        D = self.shifts.learned_directions
+        self._carry = torch.zeros(D, device=x.device)
+        self._carry_valid = torch.zeros((), dtype=torch.bool, device=x.device)
+        return {'crop': crop, 'x': x, 'source_code': code, 'inverted': inverted, 'params': self.source_params,
+                'angles': self.source_angles, 'loss': loss}
+
+    @torch.no_grad()
+    def target_shift_vectors(self, frames):
+        """The head chain of run_inference.py:173-178 for frames [N,H,W,3] uint8, `batch` at a time: preprocess_frames ->
+        face_detector.detect_landmarks(input_range='gan') on the crops -> shape_params(boxes=, has_face=) -> shifts.make_shift
+        against the source's rows.  Returns (x [N,3,256,256] the target crops, sv [N,D] before any policy, ok [N] bool =
+        has_face on the frame & valid crop & has_face on the crop)."""
+        from .face_detector import detect_landmarks
+        from .train_step import shape_params
+        xs, svs, oks = [], [], []
+        for lo in range(0, frames.shape[0], self.batch):
+            _, x, ok = preprocess_frames(self.det, self.fan, frames[lo:lo + self.batch])
+            _, boxes, has = detect_landmarks(self.det, self.fan, x, input_range='gan')
+            params, angles = shape_params(self.det, self.fan, self.E, x, boxes=boxes, has_face=has)
+            svs.append(self.shifts.make_shift(self.source_angles, angles, self.source_params, params))
+            xs.append(x)
+            oks.append(ok & has)
+        return torch.cat(xs, 0), torch.cat(svs, 0), torch.cat(oks, 0)
+
+    @torch.no_grad()
+    def reenact(self, frames, valid=None, on_fail='hold', output='video'):
+        """run_inference.py:170-195 for target frames [N,H,W,3] uint8 on the device -> (frames, ok [N] bool, shift_vectors [N,D]).
+
+        ok: has_face on the frame & valid crop & has_face on the crop & the caller's `valid` ([N] bool tensor, e.g. scene cuts).
+        on_fail: what a row that is not ok renders -- 'hold': the shift vector of the nearest earlier ok row, earlier calls since
+        set_source included (a device carry), zeros if there is none; 'source': zeros, which renders the inverted source; 'raise':
+        ONE host read, then RuntimeError naming the rows.  shift_vectors are those rendered, after the policy.
+        output: 'video' [N,256,768,3] uint8, source crop | target crop | reenacted with swap_rb (the --save_video frames,
+        run_inference.py:188-195); 'images' [N,256,256,3] uint8 RGB, reenacted only (--save_images).
+
+        Apart from on_fail='raise' nothing in this method's own code synchronises with the host; the session awaits each chunk's
+        range check one chunk behind its launches, as it always does.  The target crops of a 'video' call stay on the device until
+        it returns (0.79 MB per frame): hand a long video over in segments, the hold carry spans the calls."""
+        if on_fail not in ON_FAIL:
+            raise RuntimeError('reenact: on_fail must be one of %s, got %r' % (', '.join(ON_FAIL), on_fail))
+        if output not in OUTPUTS:
+            raise RuntimeError('reenact: output must be one of %s, got %r' % (', '.join(OUTPUTS), output))
+        frames = _device_frames(frames, 'reenact')
+        if self.session is None:
+            raise RuntimeError('reenact: no source yet (call set_source first)')
+        if frames.ndim != 4 or frames.shape[0] < 1:
+            raise RuntimeError('reenact: expected frames [N,H,W,3], got %s' % (tuple(frames.shape),))
+        n = frames.shape[0]
+        if valid is not None:
+            if not torch.is_tensor(valid) or valid.dtype != torch.bool or tuple(valid.shape) != (n,):
+                raise RuntimeError('reenact: valid must be a bool tensor [%d]' % n)
+            valid = valid.to(frames.device)
+        x, sv, ok = self.target_shift_vectors(frames.contiguous())
+        if valid is not None:
+            ok = ok & valid
+        if on_fail == 'raise':
+            bad = (~ok).cpu().nonzero().flatten().tolist()                 # the one host read
+            if bad:
+                raise RuntimeError('reenact: %d of %d target frames failed (no face, an invalid crop, or masked out): rows %s'
+                                   % (len(bad), n, bad))
+        elif on_fail == 'hold':
+            sv, self._carry, self._carry_valid = hold_failed_rows(sv, ok, self._carry, self._carry_valid)
+        else:
+            sv = torch.where(ok.unsqueeze(1), sv, torch.zeros_like(sv))
+        if output == 'video':
+            out = self.session.video_frames(self.source_x, x, sv, swap_rb=True)
+        else:
+            out = self.session.render(sv, as_uint8=True)
+        return out, ok, sv
