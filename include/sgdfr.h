@@ -38,6 +38,7 @@
  *                              run_facial_editing.py:172-189 and libs/utilities/visualization.py:46-60, for all ladders at once
  *   sgdfr_sweep_frames_f32     face_pool (AdaptiveAvgPool2d), add_border, tensor_to_image + astype(uint8) of the same scripts
  *   sgdfr_video_frames_f32     face_pool + generate_grid_image + tensor_to_image + np.uint8 + cvtColor of run_inference.py:180-195
+ *   sgdfr_video_frames_px      the same frames from the uint8 target crops of preprocess_image (utils_inference.py:61-82), unconverted
  */
 #ifndef SGDFR_H
 #define SGDFR_H
@@ -551,6 +552,31 @@ int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const int* is_st
  * when P*f is a multiple of 4 and x is 16-byte aligned, dword loads of the same elements otherwise; byte stores.  No atomics, no LDS. */
 int sgdfr_video_frames_f32(const float* x, int B, int P, int f, const float* const* panels, const int64_t* bstrides, int n_left,
                            unsigned char* frames, int swap_rb, void* stream);
+
+/* One left panel of sgdfr_video_frames_px: a table of `rows` images on the device.  kind SGDFR_PANEL_F32: float32 planar
+ * [rows,3,P,P] in [-1,1], as sgdfr_video_frames_f32 takes them; SGDFR_PANEL_U8: uint8 interleaved [rows,P,P,3] RGB, the alignment
+ * crop's own bytes (sgdfr_facecrop_forward_u8).  Frame b shows row index[b] of the table when `index` (device int32 [B]) is given,
+ * clamped into [0, rows): a bad index shows a wrong row and never reads outside the table.  Without an index rows is B (frame b
+ * shows row b) or 1 (the same image in every frame).  data NULL leaves the panel's columns of `frames` as they are. */
+#define SGDFR_PANEL_F32 0
+#define SGDFR_PANEL_U8 1
+struct sgdfr_video_panel {
+    const void* data;
+    const int* index;
+    int kind;
+    int rows;
+};
+
+/* sgdfr_video_frames_f32 with typed, indexed left panels (`panels`: a HOST array of n_left <= 3 descriptors) and an optional x:
+ * x NULL leaves the last panel of `frames` as it is (the generator's last ToRGB launch has already written it, sgdfr_torgb_finish_u8_f32)
+ * and f is then ignored.  A float32 panel gives the bytes sgdfr_video_frames_f32 gives.  A uint8 byte u goes through the two maps its
+ * float crop goes through: the crop kernel's fl32(u / 255) * 2 - 1, then sgdfr_image_to_u8_f32's trunc((v + 1) / (2 + 1e-5) * 255)
+ * -- not the identity: the 1e-5 in the divisor makes every u >= 1 come out as u - 1 (0 stays 0).  The pooled panel, swap_rb, the
+ * 16-byte loads of x and the dword path are sgdfr_video_frames_f32's; a lane reads the 3 * (4 / f) consecutive bytes of its pixels
+ * from a uint8 panel (as dwords where they are whole aligned dwords), so a wave reads one contiguous span of a panel row.  Byte
+ * stores.  No atomics, no LDS. */
+int sgdfr_video_frames_px(const float* x, int B, int P, int f, const struct sgdfr_video_panel* panels, int n_left,
+                          unsigned char* frames, int swap_rb, void* stream);
 
 /* ---- backward helpers (autograd of model.py:232-359 as restated in SURVEY.md Appendix C) ------------------------ */
 

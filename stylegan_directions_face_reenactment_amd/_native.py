@@ -234,6 +234,15 @@ SIGNATURES['sgdfr_sweep_rows_host'] = [ctypes.c_void_p, ctypes.POINTER(Direction
 SIGNATURES['sgdfr_sweep_frames_f32'] = [_c_f32p, _i, _i, _i, _ip, _c_f32p, _i64, _c_f32p, _c_f32p, _u8p, _i, ctypes.c_void_p]
 SIGNATURES['sgdfr_video_frames_f32'] = [_c_f32p, _i, _i, _i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), _i, _u8p, _i,
                                         ctypes.c_void_p]
+
+
+class VideoPanel(ctypes.Structure):
+    """struct sgdfr_video_panel (include/sgdfr.h)."""
+    _fields_ = [('data', ctypes.c_void_p), ('index', ctypes.c_void_p), ('kind', ctypes.c_int), ('rows', ctypes.c_int)]
+
+
+PANEL_F32, PANEL_U8 = 0, 1               # include/sgdfr.h SGDFR_PANEL_*
+SIGNATURES['sgdfr_video_frames_px'] = [_c_f32p, _i, _i, _i, ctypes.POINTER(VideoPanel), _i, _u8p, _i, ctypes.c_void_p]
 E4E_PARAMS_256 = 423  # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)

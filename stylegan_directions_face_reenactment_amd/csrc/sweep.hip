@@ -8,6 +8,7 @@
 //   sweep_rows    one thread per ladder row: the [R, D] one-hot matrix, the row -> direction map and the `start` flag
 //   sweep_frames  one pass over the rendered rows: f x f mean, red border on the start rows, uint8 gif frames
 //   video_frames  the same pass for the reenactment video: f x f mean next to up to three left panels, uint8 grid frames
+//   video_px      video_frames with left panels that are float32 or uint8 and read through a row index; x may be absent
 //
 // The ladder arithmetic mirrors the reference's mixed NumPy / torch dtypes operation by operation -- the lengths depend on it:
 //   angle directions   a 0-d float32 array times a Python number is float32, the division by the float64 angle scale and everything
@@ -334,6 +335,137 @@ __global__ __launch_bounds__(256) void video_frames_scalar_kernel(const float* _
     }
 }
 
+// ---------------------------------------------------------------- video frames from typed, indexed panels
+// The pass above with left panels that are float32 planar [rows,3,P,P] or uint8 interleaved [rows,P,P,3] (the alignment crop's own
+// bytes), each read at row index[b] of its table (clamped into the table), at row b, or at its only row; x may be absent.
+struct PxPanels {
+    const void* data[kVideoLeft];
+    const int* index[kVideoLeft];
+    int kind[kVideoLeft];
+    int rows[kVideoLeft];
+    int n;                                             // left panels; the pooled rows go into panel n
+};
+
+// the float the alignment crop hands on for byte u (resize_v_kernel, facecrop.hip): u / 255 * 2 - 1 in that float32 order
+__device__ __forceinline__ float u8_to_gan(unsigned char u) { return __fdiv_rn((float)u, 255.0f) * 2.0f - 1.0f; }
+
+__device__ __forceinline__ int panel_row(const PxPanels& g, int k, int b) {
+    const int rows = g.rows[k];
+    const int r = g.index[k] ? g.index[k][b] : (rows == 1 ? 0 : b);
+    return min(max(r, 0), rows - 1);                   // a bad index reads a wrong row of the table, never outside it
+}
+
+// NB consecutive bytes of a uint8 panel: dwords where the lane's span is a whole number of them and starts on one, bytes otherwise.
+// Adjacent lanes own adjacent spans, so a wave reads 64 * NB contiguous bytes of a panel row either way.
+template <int NB>
+__device__ __forceinline__ void load_span(const unsigned char* __restrict__ s, unsigned char (&u)[NB]) {
+    if (NB % 4 == 0 && (reinterpret_cast<uintptr_t>(s) & 3) == 0) {
+#pragma unroll
+        for (int i = 0; i < NB / 4; ++i) {
+            const unsigned int w = reinterpret_cast<const unsigned int*>(s)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) u[i * 4 + j] = (unsigned char)((w >> (8 * j)) & 255u);
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) u[i] = s[i];
+}
+
+// NPIX consecutive output pixels (b, oy, ox0 ..) of every panel; v[c][p] = the pooled value, stored only when `last`
+template <int NPIX>
+__device__ __forceinline__ void put_px_pixels(const PxPanels& g, unsigned char* __restrict__ frames, int b, int oy, int ox0, int P,
+                                              int swap_rb, bool last, const float (&v)[3][NPIX]) {
+    const int64_t PP = (int64_t)P * P;
+    unsigned char* line = frames + ((int64_t)b * P + oy) * (int64_t)(g.n + 1) * P * 3 + (int64_t)ox0 * 3;
+#pragma unroll
+    for (int k = 0; k < kVideoLeft; ++k) {
+        if (k >= g.n) break;
+        if (g.data[k]) {
+            const int r = panel_row(g, k, b);
+            if (g.kind[k] == SGDFR_PANEL_U8) {
+                unsigned char u[3 * NPIX];
+                load_span<3 * NPIX>(static_cast<const unsigned char*>(g.data[k]) + ((int64_t)r * PP + (int64_t)oy * P + ox0) * 3, u);
+#pragma unroll
+                for (int p = 0; p < NPIX; ++p)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) line[p * 3 + (swap_rb ? 2 - c : c)] = to_u8(u8_to_gan(u[p * 3 + c]));
+            } else {
+                const float* s = static_cast<const float*>(g.data[k]) + (int64_t)r * 3 * PP + (int64_t)oy * P + ox0;
+#pragma unroll
+                for (int p = 0; p < NPIX; ++p)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) line[p * 3 + (swap_rb ? 2 - c : c)] = to_u8(s[c * PP + p]);
+            }
+        }
+        line += (int64_t)P * 3;
+    }
+    if (last) {
+#pragma unroll
+        for (int p = 0; p < NPIX; ++p)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) line[p * 3 + (swap_rb ? 2 - c : c)] = to_u8(v[c][p]);
+    }
+}
+
+// the lane scheme of video_frames_vec_kernel; without x (F = 1) a lane converts four pixels of every left panel and stops there
+template <int F>
+__global__ __launch_bounds__(256) void video_px_vec_kernel(const float* __restrict__ x, PxPanels g, unsigned char* __restrict__ frames,
+                                                           int B, int P, int swap_rb) {
+    constexpr int NPIX = 4 / F;
+    const int W = P * F, Q = W / 4;
+    const int64_t items = (int64_t)B * P * Q, plane = (int64_t)W * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % Q);
+        const int64_t t = i / Q;
+        const int oy = (int)(t % P), b = (int)(t / P);
+        float v[3][NPIX] = {};
+        if (x) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int p = 0; p < NPIX; ++p) v[c][p] = 0.f;
+                const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * F * W + (int64_t)q * 4;
+#pragma unroll
+                for (int dy = 0; dy < F; ++dy) {
+                    const float4 e4 = *reinterpret_cast<const float4*>(xp + (int64_t)dy * W);
+                    const float e[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[c][j / F] += e[j];
+                }
+#pragma unroll
+                for (int p = 0; p < NPIX; ++p) v[c][p] = v[c][p] / (float)(F * F);
+            }
+        }
+        put_px_pixels<NPIX>(g, frames, b, oy, q * NPIX, P, swap_rb, x != nullptr, v);
+    }
+}
+
+// dword path: one output pixel per lane, the same order of additions
+__global__ __launch_bounds__(256) void video_px_scalar_kernel(const float* __restrict__ x, PxPanels g, unsigned char* __restrict__ frames,
+                                                              int B, int P, int f, int swap_rb) {
+    const int W = P * f;
+    const int64_t items = (int64_t)B * P * P, plane = (int64_t)W * W;
+    const float ff = (float)(f * f);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(i % P);
+        const int64_t t = i / P;
+        const int oy = (int)(t % P), b = (int)(t / P);
+        float v[3][1] = {};
+        if (x) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * f * W + (int64_t)ox * f;
+                float s = 0.f;
+                for (int dy = 0; dy < f; ++dy)
+                    for (int dx = 0; dx < f; ++dx) s += xp[(int64_t)dy * W + dx];
+                v[c][0] = s / ff;
+            }
+        }
+        put_px_pixels<1>(g, frames, b, oy, ox, P, swap_rb, x != nullptr, v);
+    }
+}
+
 static int gather_table(const char* who, const sgdfr_direction* table, int D, const int* dirs, int K, int pose_dim, int exp_dim,
                         SweepTable* out) {
     SGDFR_REQUIRE(table && D >= 1 && D <= SGDFR_MAX_DIRECTIONS, "%s: 1..%d directions, got %d", who, SGDFR_MAX_DIRECTIONS, D);
@@ -484,4 +616,43 @@ extern "C" int sgdfr_video_frames_f32(const float* x, int B, int P, int f, const
     else if (f == 2) hipLaunchKernelGGL(video_frames_vec_kernel<2>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
     else hipLaunchKernelGGL(video_frames_vec_kernel<4>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
     return check_launch("video_frames");
+}
+
+extern "C" int sgdfr_video_frames_px(const float* x, int B, int P, int f, const struct sgdfr_video_panel* panels, int n_left,
+                                     unsigned char* frames, int swap_rb, void* stream) {
+    SGDFR_REQUIRE(f == 1 || f == 2 || f == 4, "video_frames_px: the pooling factor must be 1, 2 or 4 (256, 512, 1024 generators), got %d", f);
+    SGDFR_REQUIRE(B >= 0 && P >= 1 && P <= 8192, "video_frames_px: bad shape B=%d P=%d", B, P);
+    SGDFR_REQUIRE(n_left >= 0 && n_left <= kVideoLeft, "video_frames_px: %d left panels (0..%d)", n_left, kVideoLeft);
+    SGDFR_REQUIRE(n_left == 0 || panels, "video_frames_px: left panels without their descriptor array");
+    PxPanels g{};
+    g.n = n_left;
+    bool any = x != nullptr;
+    for (int k = 0; k < n_left; ++k) {
+        const sgdfr_video_panel& p = panels[k];
+        g.rows[k] = 1;
+        if (!p.data) continue;
+        SGDFR_REQUIRE(p.kind == SGDFR_PANEL_F32 || p.kind == SGDFR_PANEL_U8, "video_frames_px: panel %d has kind %d (0 = float32 planar, 1 = uint8 interleaved)", k, p.kind);
+        SGDFR_REQUIRE(p.rows >= 1, "video_frames_px: panel %d has %d rows", k, p.rows);
+        SGDFR_REQUIRE(p.index || p.rows == 1 || p.rows == B, "video_frames_px: panel %d without an index has 1 or %d rows, got %d", k, B, p.rows);
+        g.data[k] = p.data;
+        g.index[k] = p.index;
+        g.kind[k] = p.kind;
+        g.rows[k] = p.rows;
+        any = true;
+    }
+    if (B == 0 || !any) return 0;
+    SGDFR_REQUIRE(frames, "video_frames_px: null frames pointer");
+    if (!x) f = 1;                                      // nothing to pool: the lanes walk the output pixels
+    const int W = P * f;
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    const int64_t items = vec ? (int64_t)B * P * (W / 4) : (int64_t)B * P * P;
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    const dim3 grid((unsigned)blocks), block(256);
+    hipStream_t st = as_stream(stream);
+    if (!vec) hipLaunchKernelGGL(video_px_scalar_kernel, grid, block, 0, st, x, g, frames, B, P, f, swap_rb);
+    else if (f == 1) hipLaunchKernelGGL(video_px_vec_kernel<1>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    else if (f == 2) hipLaunchKernelGGL(video_px_vec_kernel<2>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    else hipLaunchKernelGGL(video_px_vec_kernel<4>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    return check_launch("video_frames_px");
 }

@@ -136,6 +136,119 @@ def video_frames_uint8(x, panels=(), P=None, swap_rb=False, out=None):
     return out
 
 
+def uint8_panel_map():
+    """The byte a uint8 panel byte u becomes in a frame, for u = 0..255, as a [256] uint8 CPU tensor: the alignment crop's float
+    fl32(u / 255) * 2 - 1 (face_crop.crop_using_landmarks(as_tensor=True)) through images_to_uint8's trunc((v + 1) / (2 + 1e-5) * 255),
+    every operation in float32.  Not the identity: the 1e-5 in the divisor pulls u * (1 - 5e-6) below u and truncation then gives
+    u - 1 for every u >= 1 (0 stays 0).  ``sgdfr_video_frames_px`` evaluates the two expressions per byte; this table restates them
+    for the tests and for callers that want the target panel's bytes without a launch."""
+    u = torch.arange(256, dtype=torch.float32)
+    v = ((u / 255.0) * 2.0 - 1.0).clamp(-1.0, 1.0)
+    den = torch.tensor(2.0, dtype=torch.float32) + torch.tensor(1e-5, dtype=torch.float32)
+    return ((v + 1.0) / den * 255.0).to(torch.uint8)
+
+
+# the byte of the float 0.0 that the alignment crop writes into every pixel of an INVALID row's x: trunc(1 / (2 + 1e-5) * 255)
+BLANK_BYTE = 127
+
+
+def video_frames_px(x, panels, P=None, swap_rb=False, out=None, index=None):
+    """video_frames_uint8 with typed, indexed left panels and an optional x, in ONE launch (``sgdfr_video_frames_px``).
+
+    x: [B,3,P*f,P*f] float32 as video_frames_uint8 takes it, or None = leave the last panel of `out` as it is (the generator's last
+    ToRGB launch has written it: functional.U8Target).  panels: up to three of None (skipped: `out` keeps it), a float32 table
+    [rows,3,P,P] in [-1,1], or a uint8 table [rows,P,P,3] RGB (the crops preprocess_frames returns).  index: None, one int32 device
+    tensor [B] for every given panel, or one entry (None or such a tensor) per panel; frame b shows row index[b] of the panel's table,
+    clamped into it by the kernel.  Without an index a table has B rows or 1 (shown in every frame).  -> [B,P,K*P,3] uint8,
+    K = len(panels) + 1.  A float32 panel gives video_frames_uint8's bytes; a uint8 panel gives the bytes its float crop
+    u / 255 * 2 - 1 gives there (uint8_panel_map), which is not the identity."""
+    who = 'video_frames_px'
+    panels = list(panels)
+    if len(panels) > 3:
+        raise RuntimeError('%s takes up to 3 left panels, got %d' % (who, len(panels)))
+    K = len(panels) + 1
+    if x is not None:
+        if not torch.is_tensor(x) or x.dtype != torch.float32:
+            raise RuntimeError('%s: x must be a float32 device tensor or None, got %s' % (who, x.dtype if torch.is_tensor(x) else type(x)))
+        N.require_device(x)
+        x = N.f32c(x)
+        if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise RuntimeError('%s: expected square RGB images [B,3,S,S], got %s' % (who, tuple(x.shape)))
+        B, S = x.shape[0], x.shape[2]
+        if P is None:
+            P = min(S, 256)
+        f = _pool_factor(S, P)
+        device = x.device
+    else:
+        if out is None or not torch.is_tensor(out) or out.ndim != 4:
+            raise RuntimeError('%s: a skipped panel needs the `out` tensor that already holds it (x=None skips the last one)' % who)
+        B, f, device = out.shape[0], 1, out.device
+        if P is None:
+            P = out.shape[1]
+    if index is None or torch.is_tensor(index):
+        index = [index] * len(panels)
+    else:
+        index = list(index)
+        if len(index) != len(panels):
+            raise RuntimeError('%s: %d index entries for %d panels' % (who, len(index), len(panels)))
+    descs = (N.VideoPanel * max(len(panels), 1))()
+    keep = []                                                               # the tensors behind the descriptors' pointers
+    for k, (p, ix) in enumerate(zip(panels, index)):
+        if p is None:
+            continue
+        if not torch.is_tensor(p):
+            raise RuntimeError('%s: panel %d must be a tensor or None, got %s' % (who, k, type(p)))
+        if p.dtype == torch.uint8:
+            kind, tail = N.PANEL_U8, (P, P, 3)
+        elif p.dtype == torch.float32:
+            kind, tail = N.PANEL_F32, (3, P, P)
+        else:
+            raise RuntimeError('%s: panel %d must be float32 [rows,3,P,P] or uint8 [rows,P,P,3], got %s' % (who, k, p.dtype))
+        if ix is not None and (not torch.is_tensor(ix) or ix.dtype != torch.int32):
+            raise RuntimeError('%s: the index of panel %d must be an int32 device tensor [%d], got %s'
+                               % (who, k, B, ix.dtype if torch.is_tensor(ix) else type(ix)))
+        for t in (p, ix):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError('expected a GPU (HIP) tensor, got device %s: this package has no CPU path' % t.device)
+        p = p if p.ndim == 4 else p.unsqueeze(0)
+        if p.ndim != 4 or tuple(p.shape[1:]) != tail or p.shape[0] < 1:
+            raise RuntimeError('%s: left panels must be [rows,%d,%d,%d] (%s), got %s'
+                               % (who, tail[0], tail[1], tail[2], str(p.dtype).replace('torch.', ''), tuple(p.shape)))
+        p = p.contiguous()
+        if ix is not None:
+            if tuple(ix.shape) != (B,) or not ix.is_contiguous():
+                raise RuntimeError('%s: the index of panel %d must be a contiguous [%d] tensor, got %s' % (who, k, B, tuple(ix.shape)))
+            keep.append(ix)
+        elif p.shape[0] not in (1, B):
+            raise RuntimeError('%s: left panels without an index must have 1 or %d rows, got %s' % (who, B, tuple(p.shape)))
+        keep.append(p)
+        descs[k].data, descs[k].index = p.data_ptr(), (None if ix is None else ix.data_ptr())
+        descs[k].kind, descs[k].rows = kind, p.shape[0]
+    if out is None:
+        if any(p is None for p in panels):
+            raise RuntimeError('%s: a skipped panel needs the `out` tensor that already holds it' % who)
+        out = torch.empty(B, P, K * P, 3, device=device, dtype=torch.uint8)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (B, P, K * P, 3) or out.dtype != torch.uint8 or not out.is_cuda \
+            or not out.is_contiguous():
+        raise RuntimeError('%s: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (who, B, P, K * P))
+    N.call('sgdfr_video_frames_px', N.ptr(x), B, P, f, descs, len(panels), N.ptr(out), int(bool(swap_rb)), N.stream())
+    return out
+
+
+def hold_failed_rows_many(sv, ok):
+    """hold_failed_rows for S sources at once, each starting from an empty carry: sv [S,N,D], ok [N] (the targets' alone, so the
+    row every failed row takes is found once) -> [S,N,D].  Equal to S hold_failed_rows(sv[s], ok, zeros, False) calls bit for bit;
+    nothing is carried out.  Plain torch on the tensors' device (CPU tensors too), no host read."""
+    n = sv.shape[1]
+    if n == 0:
+        return sv
+    ok = ok.to(torch.bool)
+    idx = torch.arange(n, device=sv.device)
+    last = torch.cummax(torch.where(ok, idx, torch.full_like(idx, -1)), 0).values
+    held = torch.where((last >= 0).view(1, n, 1), sv.index_select(1, last.clamp(min=0)), torch.zeros((), dtype=sv.dtype, device=sv.device))
+    return torch.where(ok.view(1, n, 1), sv, held)
+
+
 def hold_failed_rows(sv, ok, carry, carry_valid):
     """The 'hold' policy for target frames that failed: every row of sv [N,D] whose `ok` [N] (bool) is False takes the vector of the
     nearest earlier ok row; before the first ok row it takes `carry` [D] when `carry_valid` (0-d bool tensor) is set -- the last good
@@ -194,13 +307,19 @@ def preprocess_frames(det, fan, frames, out_size=256):
     (face_crop.crop_using_landmarks).  Returns (crops [B,S,S,3] uint8, x [B,3,S,S] float32 in [-1,1], ok [B] bool) with
     ok = has_face & valid; x feeds `invert_images` directly.  One stream, no host synchronisation; rows with ok False hold nothing
     of use."""
+    crops, x, has_face, valid = _preprocess(det, fan, frames, out_size)
+    return crops, x, has_face & valid
+
+
+def _preprocess(det, fan, frames, out_size=256):
+    """preprocess_frames with its two flags apart: (crops, x, has_face [B] bool, valid [B] bool, the crop's own flag)."""
     from . import face_crop
     from .face_detector import detect_landmarks
     face_crop._check_frames(frames)
     images = frames.permute(0, 3, 1, 2).float()
     pts, _, has_face = detect_landmarks(det, fan, images, rule='last_above_0.99', input_range='255')
     (crops, x), valid = face_crop.crop_using_landmarks(frames, pts.contiguous(), out_size=out_size, as_tensor=True)
-    return crops, x, has_face & (valid != 0)
+    return crops, x, has_face, valid != 0
 
 
 def load_latent_codes(paths, device=None):
@@ -417,23 +536,40 @@ class ReenactmentSession:
                                                       as_uint8=as_uint8)), 0)
 
     @torch.no_grad()
-    def video_frames(self, source_image, target_images, shift_vectors, swap_rb=True):
-        """source | target | reenacted frames [N,H,3W,3] uint8 (the --save_video output of run_inference.py:186-198)."""
+    def video_frames(self, source_image, target_images, shift_vectors, swap_rb=True, out=None):
+        """source | target | reenacted frames [N,H,3W,3] uint8 (the --save_video output of run_inference.py:186-198).
+        target_images: [N,3,H,W] float32 in [-1,1], or the uint8 crops [N,H,W,3] themselves (preprocess_frames' first result): the
+        grid launch then reads a quarter of the bytes and no float crop has to exist (video_frames_px; the bytes are those of the
+        float crop u / 255 * 2 - 1).  A float input takes the launches it always took.  out: a contiguous uint8 [N,H,3W,3] device
+        tensor to write into (a slice of a larger result)."""
         n = shift_vectors.shape[0]
         H, W = source_image.shape[-2], source_image.shape[-1]
-        video = torch.empty(n, H, 3 * W, 3, device=shift_vectors.device, dtype=torch.uint8)
+        as_bytes = target_images.dtype == torch.uint8
+        if as_bytes and (H != W or tuple(target_images.shape) != (n, H, W, 3)):
+            raise RuntimeError('video_frames: uint8 target crops must be [%d,%d,%d,3] next to a square source panel, got %s'
+                               % (n, H, W, tuple(target_images.shape)))
+        if out is None:
+            video = torch.empty(n, H, 3 * W, 3, device=shift_vectors.device, dtype=torch.uint8)
+        elif tuple(out.shape) != (n, H, 3 * W, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise RuntimeError('video_frames: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (n, H, 3 * W))
+        else:
+            video = out
         if self.pool_to is not None:
             if (H, W) != (self.pool_to, self.pool_to):
                 raise RuntimeError('video_frames: this session pools to %d, the source panel is %d x %d' % (self.pool_to, H, W))
+            fused = video_frames_px if as_bytes else video_frames_uint8
             for lo, sv, u8, img, graphed in self._pipeline(shift_vectors, None):
                 b = sv.shape[0]
-                video_frames_uint8(img, [source_image, target_images[lo:lo + b]], self.pool_to, swap_rb=swap_rb, out=video[lo:lo + b])
+                fused(img, [source_image, target_images[lo:lo + b]], self.pool_to, swap_rb=swap_rb, out=video[lo:lo + b])
             return video
         # eager chunks: the reenacted panel is written by the generator's last launch; the other two by one grid launch
         target_for = lambda lo, b: F_.U8Target(video[lo:lo + b], panel=2, swap_rb=swap_rb)
         for lo, sv, u8, img, graphed in self._pipeline(shift_vectors, target_for):
             frames = video[lo:lo + sv.shape[0]]
-            grid_frames_uint8([source_image, target_images[lo:lo + sv.shape[0]], img if graphed else None], swap_rb=swap_rb, out=frames)
+            if as_bytes:
+                video_frames_px(img if graphed else None, [source_image, target_images[lo:lo + sv.shape[0]]], H, swap_rb=swap_rb, out=frames)
+            else:
+                grid_frames_uint8([source_image, target_images[lo:lo + sv.shape[0]], img if graphed else None], swap_rb=swap_rb, out=frames)
         return video
 
 
@@ -441,11 +577,112 @@ ON_FAIL = ('hold', 'source', 'raise')
 OUTPUTS = ('video', 'images')
 
 
+def _raise_failed_rows(who, ok):
+    """on_fail='raise': ONE host read, then RuntimeError naming the rows that are not ok."""
+    bad = (~ok).cpu().nonzero().flatten().tolist()                         # the one host read
+    if bad:
+        raise RuntimeError('%s: %d of %d target frames failed (no face, an invalid crop, or masked out): rows %s'
+                           % (who, len(bad), ok.shape[0], bad))
+
+
 def _device_frames(frames, who):
     if not torch.is_tensor(frames):
         raise RuntimeError('%s: expected a uint8 tensor of frames, got %s' % (who, type(frames)))
     N.require_device(frames, dtype=torch.uint8)
     return frames
+
+
+_ANALYSIS_FIELDS = ('crops', 'angles', 'ok', 'valid')
+
+
+class TargetAnalysis:
+    """What the heads find in N target frames, kept small: everything `Reenactor.reenact` needs of them, and nothing of any source.
+
+        crops  [N,256,256,3] uint8   the alignment crops, the bytes preprocess_frames returns (an invalid row is zeros)
+        params {key: [N,.]}          train_step.shape_params of the crops, rows concatenated
+        angles [N,3]
+        ok     [N] bool              has_face on the frame & valid crop & has_face on the crop
+        valid  [N] bool              the crop's own flag: the float crop of an invalid row is 0.0 where its bytes would map to -1,
+                                     so the target panel needs it to show such a row as `reenact` shows it (BLANK_BYTE)
+        batch  int                   the chunking it was made with (the heads' results depend on it in the last bits)
+
+    0.20 MB a frame.  len(a), a[lo:hi] (views), TargetAnalysis.cat([...]), a.to(device), a.as_dict() / TargetAnalysis.from_dict(d):
+    plain tensors and ints, so torch.save / torch.load make a cache across processes.  cat of analyses made segment by segment equals
+    the analysis of the whole bit for bit when every segment boundary is a multiple of `batch`: the chunks are then the same chunks."""
+
+    def __init__(self, crops, params, angles, ok, valid, batch):
+        n = crops.shape[0] if torch.is_tensor(crops) and crops.ndim == 4 else -1
+        if n < 0 or crops.dtype != torch.uint8 or crops.shape[3] != 3 or crops.shape[1] != crops.shape[2]:
+            raise RuntimeError('TargetAnalysis: crops must be a uint8 tensor [N,S,S,3]')
+        if not isinstance(params, dict) or not params or not all(torch.is_tensor(v) and v.ndim == 2 and v.shape[0] == n for v in params.values()):
+            raise RuntimeError('TargetAnalysis: params must be a dict of [%d,.] tensors' % n)
+        if not torch.is_tensor(angles) or tuple(angles.shape) != (n, 3):
+            raise RuntimeError('TargetAnalysis: angles must be [%d,3]' % n)
+        for name, t in (('ok', ok), ('valid', valid)):
+            if not torch.is_tensor(t) or t.dtype != torch.bool or tuple(t.shape) != (n,):
+                raise RuntimeError('TargetAnalysis: %s must be a bool tensor [%d]' % (name, n))
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise RuntimeError('TargetAnalysis: batch must be a positive int, got %r' % (batch,))
+        if len({t.device for t in [crops, angles, ok, valid] + list(params.values())}) != 1:
+            raise RuntimeError('TargetAnalysis: all tensors must live on one device')
+        self.crops, self.params, self.angles, self.ok, self.valid, self.batch = crops, dict(params), angles, ok, valid, batch
+
+    def __len__(self):
+        return self.crops.shape[0]
+
+    @property
+    def device(self):
+        return self.crops.device
+
+    def __getitem__(self, rows):
+        if not isinstance(rows, slice) or rows.step not in (None, 1):
+            raise RuntimeError('TargetAnalysis: index with a slice lo:hi (the rows stay in order; views, nothing is copied)')
+        return TargetAnalysis(self.crops[rows], {k: v[rows] for k, v in self.params.items()}, self.angles[rows], self.ok[rows],
+                              self.valid[rows], self.batch)
+
+    @staticmethod
+    def cat(analyses):
+        analyses = list(analyses)
+        if not analyses or not all(isinstance(a, TargetAnalysis) for a in analyses):
+            raise RuntimeError('TargetAnalysis.cat: expected a non-empty list of TargetAnalysis')
+        first = analyses[0]
+        for a in analyses[1:]:
+            if a.batch != first.batch:
+                raise RuntimeError('TargetAnalysis.cat: analyses made with different batch sizes (%d and %d)' % (first.batch, a.batch))
+            if list(a.params) != list(first.params):
+                raise RuntimeError('TargetAnalysis.cat: analyses with different param keys (%s and %s)' % (list(first.params), list(a.params)))
+        join = lambda get: torch.cat([get(a) for a in analyses], 0)
+        return TargetAnalysis(join(lambda a: a.crops), {k: join(lambda a, k=k: a.params[k]) for k in first.params},
+                              join(lambda a: a.angles), join(lambda a: a.ok), join(lambda a: a.valid), first.batch)
+
+    def to(self, device):
+        move = lambda t: t.to(device)
+        return TargetAnalysis(move(self.crops), {k: move(v) for k, v in self.params.items()}, move(self.angles), move(self.ok),
+                              move(self.valid), self.batch)
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name in _ANALYSIS_FIELDS}
+        d.update({'params.' + k: v for k, v in self.params.items()})
+        d['batch'] = self.batch
+        return d
+
+    @staticmethod
+    def from_dict(d):
+        missing = [k for k in _ANALYSIS_FIELDS + ('batch',) if k not in d]
+        if missing:
+            raise RuntimeError('TargetAnalysis.from_dict: the dict lacks %s' % missing)
+        params = {k[len('params.'):]: v for k, v in d.items() if k.startswith('params.')}
+        return TargetAnalysis(d['crops'], params, d['angles'], d['ok'], d['valid'], int(d['batch']))
+
+
+class Source:
+    """One source identity as `Reenactor.make_source` prepares it: code (the e4e W+ code), G_source (the generator that renders it:
+    the PTI-tuned copy, or the base generator itself), x [1,3,256,256] and crop [1,256,256,3] (the cropped real image), params /
+    angles (its 3DMM parameters), inverted (the e4e inversion before PTI), loss (the last PTI loss, a 0-d device tensor, or None)."""
+
+    def __init__(self, code, G_source, x, crop, params, angles, inverted, loss):
+        self.code, self.G_source, self.x, self.crop = code, G_source, x, crop
+        self.params, self.angles, self.inverted, self.loss = params, angles, inverted, loss
 
 
 class Reenactor:
@@ -460,6 +697,15 @@ class Reenactor:
     set_source(optimize=True) only); batch: target frames per launch of every head and of the generator.  A generator above 256^2
     is rendered through a session that pools to 256 (ReenactmentSession(pool_to=256)), as generic.generate_image does in the
     reference's loop.  image_resize(width=1000) of the reference's preprocess_image stays with the caller.
+
+    Cross-reenactment: nearly all of a `reenact` call is the analysis of the target frames, which knows nothing of the
+    source.  `analyse` does it once, any number of sources are rendered from the result, and `cross_metrics` scores them:
+
+        a = r.analyse(frames)                             # TargetAnalysis: uint8 crops, 3DMM parameters, ok; needs no source
+        torch.save(a.as_dict(), path)                     # ... a = TargetAnalysis.from_dict(torch.load(path)).to('cuda')
+        srcs = [r.make_source(f, optimize=False) for f in source_frames]
+        videos, ok, sv = r.reenact_many(srcs, a)          # [S,N,256,768,3] uint8; each row what use_source + reenact_analysed gives
+        csim, pose, exp_error, ok_r = r.cross_metrics(srcs, a, sv, id_loss)      # [S,N] each
 
     Three deliberate deviations from the reference:
       * a target frame that fails (no face on the frame, an invalid crop, no face on the crop, or the caller's `valid` mask) is
@@ -481,13 +727,12 @@ class Reenactor:
         self.G_source = self.source_x = self.source_params = self.source_angles = None
         self._carry = self._carry_valid = None
 
-    def set_source(self, frame, optimize=True, opt_steps=200, lr=3e-3):
-        """load_source_data + run_inference.py:169 for one source frame [H,W,3] or [1,H,W,3] uint8 on the device:
+    def make_source(self, frame, optimize=True, opt_steps=200, lr=3e-3):
+        """Everything `set_source` does short of selecting the source, for one source frame [H,W,3] or [1,H,W,3] uint8 on the device:
         preprocess_frames at B=1 -> invert_images -> (optimize) finetune.optimize_g with PtiLoss(lpips, x) on a deep copy of G,
-        optimize_all=False, the Reenactor's trunc -> a ReenactmentSession on the tuned copy (on G itself without optimisation,
-        run_inference.py:121-124) -> train_step.shape_params of the crop x (the cropped real image, not the inversion) -> the
-        hold carry of `reenact` is reset.  Returns {'crop' [1,256,256,3] uint8, 'x' [1,3,256,256], 'source_code', 'inverted',
-        'params', 'angles', 'loss': the last PTI loss as a 0-d device tensor (None without optimisation)}.
+        optimize_all=False, the Reenactor's trunc (on G itself without optimisation, run_inference.py:121-124) ->
+        train_step.shape_params of the crop x (the cropped real image, not the inversion).  Returns a `Source`; the Reenactor's
+        current source and hold carry are untouched, so any number can be made and kept side by side (reenact_many).
 
         ONE host read of its own: the source's `ok` flag -- a source without a usable face raises RuntimeError (the reference exits
         there).  Nothing else in this method's own code synchronises; the heads keep their own behaviour (a verified generator
@@ -519,17 +764,68 @@ class Reenactor:
             G_source.eval()
             for p in G_source.parameters():
                 p.grad = None
-        self.G_source = G_source
-        self.session = ReenactmentSession(G_source, self.A, code, self.truncation, self.trunc, batch=self.batch, shifts=self.shifts,
-                                          pool_to=self.pool_to)
         with torch.no_grad():
-            self.source_params, self.source_angles = shape_params(self.det, self.fan, self.E, x)
-        self.source_x = x
+            params, angles = shape_params(self.det, self.fan, self.E, x)
+        return Source(code, G_source, x, crop, params, angles, inverted, loss)
+
+    def _session_for(self, source):
+        """The ReenactmentSession that renders `source` for this Reenactor, made once per Source (its streams and events with it)."""
+        kept = getattr(source, '_session', None)
+        if kept is None or kept[0] is not self or kept[1].batch != self.batch:
+            kept = (self, ReenactmentSession(source.G_source, self.A, source.code, self.truncation, self.trunc, batch=self.batch,
+                                             shifts=self.shifts, pool_to=self.pool_to))
+            source._session = kept
+        return kept[1]
+
+    def use_source(self, source):
+        """Select a `Source` made by make_source: a ReenactmentSession on its generator, its 3DMM parameters as the shift vectors'
+        source side, and the hold carry of `reenact` / `reenact_analysed` reset.  No launch, no host read."""
+        if not isinstance(source, Source):
+            raise RuntimeError('use_source: expected a Source made by make_source, got %s' % type(source))
+        self.G_source = source.G_source
+        self.session = self._session_for(source)
+        self.source_params, self.source_angles, self.source_x = source.params, source.angles, source.x
         D = self.shifts.learned_directions
-        self._carry = torch.zeros(D, device=x.device)
-        self._carry_valid = torch.zeros((), dtype=torch.bool, device=x.device)
-        return {'crop': crop, 'x': x, 'source_code': code, 'inverted': inverted, 'params': self.source_params,
-                'angles': self.source_angles, 'loss': loss}
+        self._carry = torch.zeros(D, device=source.x.device)
+        self._carry_valid = torch.zeros((), dtype=torch.bool, device=source.x.device)
+
+    def set_source(self, frame, optimize=True, opt_steps=200, lr=3e-3):
+        """load_source_data + run_inference.py:169 for one source frame [H,W,3] or [1,H,W,3] uint8 on the device: make_source
+        (crop -> e4e -> PTI on a deep copy of G -> the source's 3DMM parameters) followed by use_source (the session, the hold carry of
+        `reenact` reset).  Returns {'crop' [1,256,256,3] uint8, 'x' [1,3,256,256], 'source_code', 'inverted', 'params', 'angles',
+        'loss': the last PTI loss as a 0-d device tensor (None without optimisation)}.
+
+        ONE host read, make_source's: a source without a usable face raises RuntimeError (the reference exits there)."""
+        src = self.make_source(frame, optimize=optimize, opt_steps=opt_steps, lr=lr)
+        self.use_source(src)
+        return {'crop': src.crop, 'x': src.x, 'source_code': src.code, 'inverted': src.inverted, 'params': src.params,
+                'angles': src.angles, 'loss': src.loss}
+
+    @torch.no_grad()
+    def analyse(self, frames):
+        """The head chain of `target_shift_vectors` for frames [N,H,W,3] uint8 on the device, up to but not including make_shift, so
+        without any source (it works before set_source): `batch` frames at a time preprocess_frames -> detect_landmarks(input_range=
+        'gan') on the crops -> shape_params(boxes=, has_face=).  Returns a `TargetAnalysis`; the float crops live only inside a chunk.
+        No host synchronisation of its own."""
+        from .face_detector import detect_landmarks
+        from .train_step import shape_params
+        frames = _device_frames(frames, 'analyse')
+        if frames.ndim != 4 or frames.shape[0] < 1:
+            raise RuntimeError('analyse: expected frames [N,H,W,3], got %s' % (tuple(frames.shape),))
+        frames = frames.contiguous()
+        crops, angles, oks, valids, params = [], [], [], [], {}
+        for lo in range(0, frames.shape[0], self.batch):
+            crop, x, has_frame, valid = _preprocess(self.det, self.fan, frames[lo:lo + self.batch])
+            _, boxes, has = detect_landmarks(self.det, self.fan, x, input_range='gan')
+            p, ang = shape_params(self.det, self.fan, self.E, x, boxes=boxes, has_face=has)
+            for k, v in p.items():
+                params.setdefault(k, []).append(v)
+            crops.append(crop)
+            angles.append(ang)
+            oks.append(has_frame & valid & has)
+            valids.append(valid)
+        return TargetAnalysis(torch.cat(crops, 0), {k: torch.cat(v, 0) for k, v in params.items()}, torch.cat(angles, 0),
+                              torch.cat(oks, 0), torch.cat(valids, 0), self.batch)
 
     @torch.no_grad()
     def target_shift_vectors(self, frames):
@@ -562,7 +858,8 @@ class Reenactor:
 
         Apart from on_fail='raise' nothing in this method's own code synchronises with the host; the session awaits each chunk's
         range check one chunk behind its launches, as it always does.  The target crops of a 'video' call stay on the device until
-        it returns (0.79 MB per frame): hand a long video over in segments, the hold carry spans the calls."""
+        it returns (0.79 MB per frame): hand a long video over in segments, the hold carry spans the calls -- or `analyse` it once
+        (0.20 MB per frame, uint8) and render from that with `reenact_analysed` / `reenact_many`."""
         if on_fail not in ON_FAIL:
             raise RuntimeError('reenact: on_fail must be one of %s, got %r' % (', '.join(ON_FAIL), on_fail))
         if output not in OUTPUTS:
@@ -581,10 +878,7 @@ class Reenactor:
         if valid is not None:
             ok = ok & valid
         if on_fail == 'raise':
-            bad = (~ok).cpu().nonzero().flatten().tolist()                 # the one host read
-            if bad:
-                raise RuntimeError('reenact: %d of %d target frames failed (no face, an invalid crop, or masked out): rows %s'
-                                   % (len(bad), n, bad))
+            _raise_failed_rows('reenact', ok)
         elif on_fail == 'hold':
             sv, self._carry, self._carry_valid = hold_failed_rows(sv, ok, self._carry, self._carry_valid)
         else:
@@ -594,3 +888,126 @@ class Reenactor:
         else:
             out = self.session.render(sv, as_uint8=True)
         return out, ok, sv
+
+    def _check_analysed(self, who, analysis, valid, on_fail, output):
+        """The argument checks shared by reenact_analysed and reenact_many -> (ok [N] with the caller's mask folded in)."""
+        if on_fail not in ON_FAIL:
+            raise RuntimeError('%s: on_fail must be one of %s, got %r' % (who, ', '.join(ON_FAIL), on_fail))
+        if output not in OUTPUTS:
+            raise RuntimeError('%s: output must be one of %s, got %r' % (who, ', '.join(OUTPUTS), output))
+        if not isinstance(analysis, TargetAnalysis):
+            raise RuntimeError('%s: expected the TargetAnalysis of analyse(frames), got %s' % (who, type(analysis)))
+        n = len(analysis)
+        if valid is not None and (not torch.is_tensor(valid) or valid.dtype != torch.bool or tuple(valid.shape) != (n,)):
+            raise RuntimeError('%s: valid must be a bool tensor [%d]' % (who, n))
+        N.require_device(analysis.crops, dtype=torch.uint8)
+        N.require_device(analysis.angles, *analysis.params.values())
+        if n < 1 or tuple(analysis.crops.shape[1:]) != (256, 256, 3):
+            raise RuntimeError('%s: expected an analysis of N >= 1 crops [N,256,256,3], got %s' % (who, tuple(analysis.crops.shape)))
+        return analysis.ok if valid is None else analysis.ok & valid.to(analysis.ok.device)
+
+    def _finish_target_panel(self, video, analysis):
+        """The target panel of the rows whose crop is invalid: their float crop is 0.0 in every pixel (BLANK_BYTE in a frame), their
+        bytes are zeros (which map to -1, byte 0).  One masked fill over the panel, no host read; `video` is [...,N,256,768,3]."""
+        video[..., 256:512, :].masked_fill_(~analysis.valid.view(-1, 1, 1, 1), BLANK_BYTE)
+
+    @torch.no_grad()
+    def reenact_analysed(self, analysis, valid=None, on_fail='hold', output='video'):
+        """`reenact` from the TargetAnalysis of its frames: make_shift against the current source, the same valid / on_fail / output
+        rules, the same hold carry used and updated, the target panel converted from analysis.crops in the grid launch
+        (video_frames_px).  -> (frames, ok, shift_vectors), bit for bit what reenact(frames) returns when the analysis was made
+        with this Reenactor's batch.  No head runs.  Apart from on_fail='raise' nothing in this method's own code synchronises."""
+        ok = self._check_analysed('reenact_analysed', analysis, valid, on_fail, output)
+        if self.session is None:
+            raise RuntimeError('reenact_analysed: no source yet (call set_source or use_source first)')
+        sv = self.shifts.make_shift(self.source_angles, analysis.angles, self.source_params, analysis.params)
+        if on_fail == 'raise':
+            _raise_failed_rows('reenact_analysed', ok)
+        elif on_fail == 'hold':
+            sv, self._carry, self._carry_valid = hold_failed_rows(sv, ok, self._carry, self._carry_valid)
+        else:
+            sv = torch.where(ok.unsqueeze(1), sv, torch.zeros_like(sv))
+        if output == 'video':
+            out = self.session.video_frames(self.source_x, analysis.crops, sv, swap_rb=True)
+            self._finish_target_panel(out, analysis)
+        else:
+            out = self.session.render(sv, as_uint8=True)
+        return out, ok, sv
+
+    def _check_sources(self, who, sources):
+        sources = list(sources)
+        if not sources or not all(isinstance(s, Source) for s in sources):
+            raise RuntimeError('%s: expected a non-empty list of the Sources make_source returns' % who)
+        return sources
+
+    @torch.no_grad()
+    def reenact_many(self, sources, analysis, valid=None, on_fail='hold', output='video'):
+        """Cross-reenactment: every Source of `sources` (make_source) rendered against the same TargetAnalysis -> (frames
+        [S,N,256,768,3] uint8 for output='video' or [S,N,256,256,3] for 'images', ok [N] bool, shift_vectors [S,N,D]).  The video
+        frames are 0.59 MB per frame and source, the images 0.20 MB: slice the analysis (a[lo:hi]) where S * N of them do not fit.
+
+        Row s is what use_source(sources[s]) + reenact_analysed(analysis, ...) returns, bit for bit: each source is rendered by a
+        ReenactmentSession of its own on its own G_source (sources that share a generator object share its weight packs and graphs),
+        its N rows chunked by `batch` on their own, so a chunk never mixes sources.  ok depends on the targets alone: the rows the
+        'hold' policy copies are found once for all sources.  Every source starts from an empty carry, nothing is carried out, and
+        the Reenactor's current source and carry are untouched.  No head runs.  on_fail='raise' makes its ONE host read; nothing else
+        in this method's own code synchronises."""
+        sources = self._check_sources('reenact_many', sources)
+        ok = self._check_analysed('reenact_many', analysis, valid, on_fail, output)
+        sv = torch.stack([self.shifts.make_shift(s.angles, analysis.angles, s.params, analysis.params) for s in sources], 0)
+        if on_fail == 'raise':
+            _raise_failed_rows('reenact_many', ok)
+        elif on_fail == 'hold':
+            sv = hold_failed_rows_many(sv, ok)
+        else:
+            sv = torch.where(ok.view(1, -1, 1), sv, torch.zeros((), dtype=sv.dtype, device=sv.device))
+        n = len(analysis)
+        out = torch.empty(len(sources), n, 256, 768 if output == 'video' else 256, 3, device=sv.device, dtype=torch.uint8)
+        for s, src in enumerate(sources):
+            session = self._session_for(src)
+            if output == 'video':
+                session.video_frames(src.x, analysis.crops, sv[s], swap_rb=True, out=out[s])
+            else:
+                lo = 0
+                for chunk in session.frames(sv[s], as_uint8=True):
+                    out[s, lo:lo + chunk.shape[0]].copy_(chunk)
+                    lo += chunk.shape[0]
+        if output == 'video':
+            self._finish_target_panel(out, analysis)
+        return out, ok, sv
+
+    @torch.no_grad()
+    def cross_metrics(self, sources, analysis, shift_vectors, id_loss):
+        """The scores of cross-reenactment for every (source, target frame) pair -> (csim, pose, exp_error: [S,N] float32 each,
+        ok_reenacted [S,N] bool).  For every source, `batch` rows of `shift_vectors` [S,N,D] (reenact_many's) at a time: the float
+        renders of its session (session.frames: no uint8 detour) -> detect_landmarks(input_range='gan') + shape_params on them ->
+        train_step.evaluation_metrics against the targets' params / angles of the analysis, CSIM against the source crop x, as
+        evaluate_model_reenactment_video scores against real frames.  ok_reenacted = analysis.ok & a face was found on the render;
+        the scores of the other rows mean nothing.  id_loss: the id_loss.IDLoss head.  No host read."""
+        from .face_detector import detect_landmarks
+        from .train_step import evaluation_metrics, shape_params
+        if not isinstance(analysis, TargetAnalysis):
+            raise RuntimeError('cross_metrics: expected the TargetAnalysis of analyse(frames), got %s' % type(analysis))
+        sources = self._check_sources('cross_metrics', sources)
+        n, S = len(analysis), len(sources)
+        if not torch.is_tensor(shift_vectors) or tuple(shift_vectors.shape) != (S, n, self.shifts.learned_directions):
+            raise RuntimeError('cross_metrics: shift_vectors must be [%d,%d,%d] (reenact_many\'s third result)'
+                               % (S, n, self.shifts.learned_directions))
+        N.require_device(shift_vectors, analysis.angles)
+        if id_loss is None:
+            raise RuntimeError('cross_metrics: CSIM needs an id_loss head')
+        dev = shift_vectors.device
+        csim, pose, exp_error = (torch.empty(S, n, device=dev, dtype=torch.float32) for _ in range(3))
+        ok_reenacted = torch.empty(S, n, device=dev, dtype=torch.bool)
+        for s, src in enumerate(sources):
+            lo = 0
+            for img in self._session_for(src).frames(shift_vectors[s]):
+                hi = lo + img.shape[0]
+                _, boxes, has = detect_landmarks(self.det, self.fan, img, input_range='gan')
+                params, angles = shape_params(self.det, self.fan, self.E, img, boxes=boxes, has_face=has)
+                target = {k: v[lo:hi] for k, v in analysis.params.items()}
+                c, p, e = evaluation_metrics(self.shifts, id_loss, params, target, angles, analysis.angles[lo:hi], img, src.x)
+                csim[s, lo:hi], pose[s, lo:hi], exp_error[s, lo:hi] = c, p, e
+                ok_reenacted[s, lo:hi] = analysis.ok[lo:hi] & has
+                lo = hi
+        return csim, pose, exp_error, ok_reenacted
