@@ -8,8 +8,9 @@
 //     UP3   : 8 segments = 4 parity planes x 2 plane rows (tap (ky,kx) reads plane (ky&1,kx&1), row y+(ky>>1),
 //             column j+(kx>>1)) -- the planes produced by sgdfr_blur_adjoint_f32
 // Channel strides in LDS are odd so the MFMA fragment reads (32 lanes = 32 channels) are conflict-free.
-// Blocks own a (64 o x 64 i) tile and a contiguous range of chunks; partial sums are added to the packed
-// gradient dwp[Cin][9][Cout] with fp32 atomics.
+// Blocks own a (64 o x 64 i) tile and a contiguous range of chunks (one of K pixel slices); a slice stores its sums to
+// the partials buffer part[K][9][Cout][Cin], added in fixed order by a finish kernel (sgdfr_modconv_wgrad_parts_f32, the
+// default), or adds them to the packed gradient dwp[Cin][9][Cout] with fp32 atomics (sgdfr_modconv_wgrad_f32).
 #include "common.h"
 
 namespace sgdfr {
