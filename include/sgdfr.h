@@ -39,6 +39,7 @@
  *   sgdfr_sweep_frames_f32     face_pool (AdaptiveAvgPool2d), add_border, tensor_to_image + astype(uint8) of the same scripts
  *   sgdfr_video_frames_f32     face_pool + generate_grid_image + tensor_to_image + np.uint8 + cvtColor of run_inference.py:180-195
  *   sgdfr_video_frames_px      the same frames from the uint8 target crops of preprocess_image (utils_inference.py:61-82), unconverted
+ *   sgdfr_shaperender_forward_f32  libs/DECA/decalib/utils/renderer.py:237-293 SRenderY.render_shape (pytorch3d's rasterize_meshes there)
  */
 #ifndef SGDFR_H
 #define SGDFR_H
@@ -963,6 +964,39 @@ int sgdfr_facecrop_boxes_f32(const float* landmarks, int rows, int* boxes, int* 
 int sgdfr_facecrop_forward_u8(const uint8_t* frames, const float* landmarks, int rows, int H, int W, int out_size, int max_size,
                               uint8_t* crops, int* valid, float* e4e, int* boxes, int* sizes, float* crop_float, void* workspace,
                               int64_t workspace_bytes, void* stream);
+
+/* DECA's shape renderer (libs/DECA/decalib/utils/renderer.py:237-293 SRenderY.render_shape, :28-78 Pytorch3dRasterizer at its fixed
+ * settings, utils/util.py:193-225 vertex_normals, :227-237 batch_orth_proj with deca.py:175), csrc/shaperender.hip.  Forward only.
+ * A general triangle mesh: vertices [rows,V,3] fp32, faces [F,3] int32 shared by all rows, and the vertex -> corner table of the faces:
+ *   csr_offsets [V+1], csr_entries [3F] = face * 3 + corner of every corner that names the vertex, ascending per vertex.  The caller
+ *   vouches for index ranges; an index outside 0..V-1 only drops its face.  rows 1..4096, V and F 1..2^24.
+ * sgdfr_shaperender_normals_f32: normals [rows,V,3]: per corner k of a face the cross product (v[k+1] - v[k]) x (v[k+2] - v[k]), summed
+ *   per vertex in table order, then n / max(|n|, 1e-6); a vertex no face names gets zeros.
+ * sgdfr_shaperender_forward_f32: exactly one of cam [rows,3] = (s, tx, ty) and projected [rows,V,3].  With cam: X = s (x + tx),
+ *   Y = -s (y + ty), Z = -s z + z_offset; with projected: Z + z_offset only (render_shape uses z_offset = 10).
+ *   Rasteriser at S x S, 1..4096: the centre of pixel (row i, column j) is p = ((2j+1)/S - 1, (2i+1)/S - 1);
+ *   edge(p;u,v) = (p.x-u.x)(v.y-u.y) - (p.y-u.y)(v.x-u.x), area = edge(c;a,b), w0 = edge(p;b,c) / (area + 1e-8), w1 = edge(p;c,a) / ..,
+ *   w2 = edge(p;a,b) / ..; a face with |area| <= 1e-8 or all three Z < 0 is skipped; a pixel is covered iff w0, w1, w2 > 0 strictly
+ *   (both windings, no clipping of the barycentrics, no perspective correction); z = w0 Za + w1 Zb + w2 Zc, dropped when z < 0; the
+ *   smallest z wins, the lower face index on equal z.  These restate pytorch3d's rasterize_meshes at blur_radius 0 and one face per
+ *   pixel with the x, y flip of renderer.py:53 folded in; the tie rule is this library's.
+ *   pix_to_face [rows,S,S] int32 (-1: none; the index counts within the mesh), zbuf [rows,S,S] and bary [rows,S,S,3] (-1 where no
+ *   face covers): each may be NULL.
+ *   shape (NULL: rasterise only; vertices, the table, lights, alpha and background are then unused) [rows,3,S,S]: with N the world normal
+ *   and Tz the z of the projected vertices' normal, both interpolated with w and not re-normalised: albedo = (w0+w1+w2) 180/255,
+ *   shading_c = mean_l clamp(N . d_l, 0, 1) I_lc for lights [light_rows = 1 or rows, L <= 8, 6] = direction (normalised here), intensity;
+ *   alpha = covered (Tz < 0.15);  out = albedo shading alpha + background (1 - alpha), background [rows,3,S,S] or NULL for 0;
+ *   gan_range != 0 writes clamp(out, 0, 1) 2 - 1 instead.  alpha [rows,1,S,S] may be NULL.
+ * workspace: device scratch of at least sgdfr_shaperender_workspace_bytes(rows, V, F) bytes (-1 for sizes out of range).
+ * Five launches (project, normals twice, face setup, raster + shade), no atomics: bit-identical from call to call; no host
+ * synchronisation, everything on `stream`. */
+int64_t sgdfr_shaperender_workspace_bytes(int rows, int V, int F);
+int sgdfr_shaperender_normals_f32(const float* vertices, int rows, int V, const int* faces, int F, const int* csr_offsets,
+                                  const int* csr_entries, float* normals, void* stream);
+int sgdfr_shaperender_forward_f32(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V,
+                                  const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S, const float* lights,
+                                  int light_rows, int L, const float* background, int gan_range, float* shape, float* alpha,
+                                  int* pix_to_face, float* zbuf, float* bary, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio

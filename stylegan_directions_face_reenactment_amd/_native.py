@@ -243,6 +243,10 @@ class VideoPanel(ctypes.Structure):
 
 PANEL_F32, PANEL_U8 = 0, 1               # include/sgdfr.h SGDFR_PANEL_*
 SIGNATURES['sgdfr_video_frames_px'] = [_c_f32p, _i, _i, _i, ctypes.POINTER(VideoPanel), _i, _u8p, _i, ctypes.c_void_p]
+SIGNATURES['sgdfr_shaperender_normals_f32'] = [_c_f32p, _i, _i, _ip, _i, _ip, _ip, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_shaperender_forward_f32'] = [_c_f32p, _c_f32p, _c_f32p, _f, _i, _i, _ip, _i, _ip, _ip, _i, _c_f32p, _i, _i, _c_f32p, _i,
+                                               _c_f32p, _c_f32p, _ip, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+SHAPERENDER_MAX_LIGHTS, SHAPERENDER_MAX_SIZE = 8, 4096      # csrc/shaperender.hip kMaxLights, kMaxSize
 E4E_PARAMS_256 = 423  # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
@@ -260,6 +264,7 @@ SIZE_QUERIES = {
     'sgdfr_e4e_pack_elems': 1, 'sgdfr_e4e_debug_elems': 2, 'sgdfr_e4e_workspace_bytes': 2,
     'sgdfr_facecrop_workspace_bytes': 4,
     'sgdfr_pairloss_workspace_bytes': 1,
+    'sgdfr_shaperender_workspace_bytes': 3,
 }
 COUNT_QUERIES = ('sgdfr_e4e_style_count', 'sgdfr_e4e_param_count')      # int (int R): a count, or -1 for a resolution out of range
 

@@ -241,6 +241,30 @@ def decode(flame, codedict, image_size=224):
     return _DecodeFn.apply(shape, exp, pose, cam, flame.packed(), True, _needs_grad(shape, exp, pose, cam))
 
 
+def topology(flame):
+    """The shape_render.MeshTopology of the module's faces_tensor, built on first use and again when the buffer changes."""
+    from .shape_render import MeshTopology
+    ft = flame.faces_tensor
+    key = (ft.data_ptr(), ft._version, str(ft.device))
+    cached = flame.__dict__.get('_topology')
+    if cached is None or cached[0] != key:
+        cached = flame.__dict__['_topology'] = (key, MeshTopology.from_flame(flame))
+    return cached[1]
+
+
+def shape_images(flame, codedict, size=224, images=None, gan_range=False):
+    """The `shape_images` of DECA.decode_deca (deca.py:175-187): FLAME forward, the camera projection and SRenderY.render_shape ->
+    [B,3,size,size], the grey lit mesh over `images` (None: black).  codedict is what deca.encode / train_step.shape_params return
+    ('alpha_shp', 'alpha_exp', 'pose', 'cam') or DECA's own keys ('shape', 'exp', 'pose', 'cam').  Forward only: nothing is kept
+    for a backward.  gan_range=True: clamp(., 0, 1) * 2 - 1, a float panel for reenact.video_frames_px."""
+    from .shape_render import render_shape
+    pick = lambda a, b: codedict[a] if a in codedict else codedict[b]
+    with torch.no_grad():
+        shape, exp, pose, cam = _check_coeffs(pick('alpha_shp', 'shape'), pick('alpha_exp', 'exp'), codedict['pose'], codedict['cam'])
+        verts, _, _ = flame(shape, exp, pose)
+        return render_shape(verts, topology(flame), cam=cam, size=size, images=images, gan_range=gan_range)['shape']
+
+
 class _ShapeLossFn(torch.autograd.Function):
     """Both decodes as one batch, the three terms and their cotangents in five launches; backward: two more, for the reenacted set."""
 

@@ -235,6 +235,39 @@ def video_frames_px(x, panels, P=None, swap_rb=False, out=None, index=None):
     return out
 
 
+def shape_panels(flame, params, ok=None, size=256, batch=32):
+    """The fitted mesh of every analysed frame as a float panel: params = a `TargetAnalysis.params`-shaped dict ('alpha_shp',
+    'alpha_exp', 'pose', 'cam', [N,.] each), rendered `batch` rows at a time by flame.shape_images -> [N,3,size,size] float32 in
+    [-1,1] (clamp(shape_images, 0, 1) * 2 - 1).  Rows whose `ok` [N] (bool) is False are 0.0 everywhere, which is what the alignment
+    crop writes for an invalid row.  Whether DECA tracked the target is answered by looking at the mesh beside the frame:
+
+        a = R.analyse(frames)                                                  # Reenactor
+        mesh = shape_panels(flame, a.params, a.ok)                             # [N,3,256,256]
+        _, ok, sv = R.reenact_analysed(a, output='images')                     # the shift vectors under the on_fail policy
+        x = R.session.render(sv)                                               # the reenacted frames, float32 [N,3,256,256]
+        video = video_frames_px(x, [R.source_x, a.crops, mesh])                # source | target | target's mesh | reenacted
+    """
+    from . import flame as FL
+    keys = ('alpha_shp', 'alpha_exp', 'pose', 'cam')
+    if not isinstance(params, dict) or any(k not in params or not torch.is_tensor(params[k]) or params[k].ndim != 2 for k in keys):
+        raise RuntimeError('shape_panels: params must be a dict with [N,.] tensors under %s' % (keys,))
+    n = params['pose'].shape[0]
+    if n < 1 or any(params[k].shape[0] != n for k in keys):
+        raise RuntimeError('shape_panels: the params describe %s rows' % [params[k].shape[0] for k in keys])
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        raise RuntimeError('shape_panels: batch must be a positive int, got %r' % (batch,))
+    N.require_device(*(params[k] for k in keys))
+    if ok is not None:
+        if not torch.is_tensor(ok) or ok.dtype != torch.bool or tuple(ok.shape) != (n,) or ok.device != params['pose'].device:
+            raise RuntimeError('shape_panels: ok must be a bool tensor [%d] on the params\' device' % n)
+    out = torch.empty((n, 3, size, size), dtype=torch.float32, device=params['pose'].device)
+    for lo in range(0, n, batch):
+        out[lo:lo + batch] = FL.shape_images(flame, {k: params[k][lo:lo + batch] for k in keys}, size=size, gan_range=True)
+    if ok is not None:
+        out = torch.where(ok.view(n, 1, 1, 1), out, torch.zeros((), dtype=out.dtype, device=out.device))
+    return out
+
+
 def hold_failed_rows_many(sv, ok):
     """hold_failed_rows for S sources at once, each starting from an empty carry: sv [S,N,D], ok [N] (the targets' alone, so the
     row every failed row takes is found once) -> [S,N,D].  Equal to S hold_failed_rows(sv[s], ok, zeros, False) calls bit for bit;
