@@ -550,7 +550,9 @@ int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const int* is_st
  * f x f mean of x in sgdfr_sweep_frames_f32's arithmetic (summed row by row and left to right, divided by f*f last).  Every byte is
  * sgdfr_image_to_u8_f32's; swap_rb != 0 stores the channels in reverse order in every panel, as sgdfr_grid_to_u8_f32 does.  The
  * bytes equal sgdfr_sweep_frames_f32(pooled) followed by sgdfr_grid_to_u8_f32 without the float intermediate.  16-byte loads of x
- * when P*f is a multiple of 4 and x is 16-byte aligned, dword loads of the same elements otherwise; byte stores.  No atomics, no LDS. */
+ * when P*f is a multiple of 4 and x is 16-byte aligned, dword loads of the same elements otherwise; byte stores.  No atomics, no LDS.
+ * This entry is an adapter: it launches sgdfr_video_frames_px's kernels with every panel described as an SGDFR_PANEL_F32 table
+ * without an index, of 1 row (stride 0) or B rows; the window walk is the one under sgdfr_sweep_frames_f32 too. */
 int sgdfr_video_frames_f32(const float* x, int B, int P, int f, const float* const* panels, const int64_t* bstrides, int n_left,
                            unsigned char* frames, int swap_rb, void* stream);
 
@@ -570,7 +572,7 @@ struct sgdfr_video_panel {
 
 /* sgdfr_video_frames_f32 with typed, indexed left panels (`panels`: a HOST array of n_left <= 3 descriptors) and an optional x:
  * x NULL leaves the last panel of `frames` as it is (the generator's last ToRGB launch has already written it, sgdfr_torgb_finish_u8_f32)
- * and f is then ignored.  A float32 panel gives the bytes sgdfr_video_frames_f32 gives.  A uint8 byte u goes through the two maps its
+ * and f is then ignored.  A float32 panel gives the bytes sgdfr_video_frames_f32 gives (that entry runs these kernels).  A uint8 byte u goes through the two maps its
  * float crop goes through: the crop kernel's fl32(u / 255) * 2 - 1, then sgdfr_image_to_u8_f32's trunc((v + 1) / (2 + 1e-5) * 255)
  * -- not the identity: the 1e-5 in the divisor makes every u >= 1 come out as u - 1 (0 stays 0).  The pooled panel, swap_rb, the
  * 16-byte loads of x and the dword path are sgdfr_video_frames_f32's; a lane reads the 3 * (4 / f) consecutive bytes of its pixels

@@ -6,9 +6,10 @@
 // 1024^2 frame goes through AdaptiveAvgPool2d, clamp, scale and cast passes of its own.  Here
 //   sweep_plan    one thread per (source row, direction): start / min / max / step and the two arange lengths, on the device
 //   sweep_rows    one thread per ladder row: the [R, D] one-hot matrix, the row -> direction map and the `start` flag
-//   sweep_frames  one pass over the rendered rows: f x f mean, red border on the start rows, uint8 gif frames
-//   video_frames  the same pass for the reenactment video: f x f mean next to up to three left panels, uint8 grid frames
-//   video_px      video_frames with left panels that are float32 or uint8 and read through a row index; x may be absent
+//   pooled_walk   one pass over the rendered rows: the f x f mean of every output pixel, handed to a sink; the one walk below both
+//   sweep_frames  the walk into pooled / bordered floats (red border on the start rows) and one- or two-panel uint8 gif frames
+//   video_px      the walk into the reenactment video's uint8 grid frames, next to up to three left panels that are float32 or uint8
+//                 and read through a row index; x may be absent.  sgdfr_video_frames_f32 is these kernels on float panels
 //
 // The ladder arithmetic mirrors the reference's mixed NumPy / torch dtypes operation by operation -- the lengths depend on it:
 //   angle directions   a 0-d float32 array times a Python number is float32, the division by the float64 angle scale and everything
@@ -193,151 +194,119 @@ __device__ __forceinline__ void put_pixel(const FramesOut& o, int r, int oy, int
     }
 }
 
+template <int NPIX>
+__device__ __forceinline__ void put_pixels(const FramesOut& o, int r, int oy, int ox0, int P, const float (&v)[3][NPIX]) {
+#pragma unroll
+    for (int p = 0; p < NPIX; ++p) {
+        const float w[3] = {v[0][p], v[1][p], v[2][p]};
+        put_pixel(o, r, oy, ox0 + p, P, w);
+    }
+}
+
+// ---------------------------------------------------------------- the pooled walk
+// The one f x f window walk under every frames kernel: R rows of x [R,3,P*f,P*f], the window summed row by row, left to right, and
+// divided by f^2 last.  sink(r, oy, ox0, v) receives v[c][p] = channel c of output pixel (r, oy, ox0 + p).  Without x (uniform over
+// the launch) the lanes walk the same items and v is zeros.  `block` is blockDim.x, read by the KERNEL and handed in: read in here,
+// a device function, it is lowered before the inlining without the kernel's uniform-block promise, to a global_load_ushort and a
+// wait at the top of every kernel (+ 4.8 % on the two-panel sweep frames).
+// What the sinks capture is settled per kernel by the build and the clock (profiles/frames_walk_time.txt), not by rule: the sweep
+// sink copies FramesOut BY VALUE, as conv_tile.h advises; the px sink refers to the kernel's arguments, because a by-value copy of
+// PxPanels is split into scalars, the float and uint8 branches of a panel are then merged behind a common conversion and store, and
+// that schedule is 1 % slower at f = 4.
+//
 // 16-byte path: a lane owns four consecutive input columns of F input rows = 4 / F whole output pixels; the lanes of a wave read
-// 1 KiB of one input row.  The F x F window is summed row by row, left to right, and divided by F^2 last.
-template <int F>
-__global__ __launch_bounds__(256) void sweep_frames_vec_kernel(const float* __restrict__ x, FramesOut o, int R, int P) {
+// 1 KiB of one input row.
+constexpr int kWalkBlock = 256;
+
+template <int F, class Sink>
+__device__ __forceinline__ void pooled_walk_vec(const float* __restrict__ x, int R, int P, int block, const Sink& sink) {
     constexpr int NPIX = 4 / F;
     const int W = P * F, Q = W / 4;
     const int64_t items = (int64_t)R * P * Q, plane = (int64_t)W * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = (int64_t)blockIdx.x * block + threadIdx.x; i < items; i += (int64_t)gridDim.x * block) {
         const int q = (int)(i % Q);
         const int64_t t = i / Q;
         const int oy = (int)(t % P), r = (int)(t / P);
-        float acc[3][NPIX];
+        float v[3][NPIX] = {};
+        if (x) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < 3; ++c) {
+                const float* xp = x + ((int64_t)r * 3 + c) * plane + (int64_t)oy * F * W + (int64_t)q * 4;
 #pragma unroll
-            for (int p = 0; p < NPIX; ++p) acc[c][p] = 0.f;
-            const float* xp = x + ((int64_t)r * 3 + c) * plane + (int64_t)oy * F * W + (int64_t)q * 4;
+                for (int dy = 0; dy < F; ++dy) {
+                    const float4 e4 = *reinterpret_cast<const float4*>(xp + (int64_t)dy * W);
+                    const float e[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
-            for (int dy = 0; dy < F; ++dy) {
-                const float4 v = *reinterpret_cast<const float4*>(xp + (int64_t)dy * W);
-                const float e[4] = {v.x, v.y, v.z, v.w};
+                    for (int j = 0; j < 4; ++j) v[c][j / F] += e[j];
+                }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[c][j / F] += e[j];
+                for (int p = 0; p < NPIX; ++p) v[c][p] = v[c][p] / (float)(F * F);
             }
         }
-#pragma unroll
-        for (int p = 0; p < NPIX; ++p) {
-            const float v[3] = {acc[0][p] / (float)(F * F), acc[1][p] / (float)(F * F), acc[2][p] / (float)(F * F)};
-            put_pixel(o, r, oy, q * NPIX + p, P, v);
-        }
+        sink(r, oy, q * NPIX, v);
     }
 }
 
 // dword path (P * f not a multiple of 4, or a pointer off 16 bytes): one output pixel per lane, the same order of additions
-__global__ __launch_bounds__(256) void sweep_frames_scalar_kernel(const float* __restrict__ x, FramesOut o, int R, int P, int f) {
+template <class Sink>
+__device__ __forceinline__ void pooled_walk_scalar(const float* __restrict__ x, int R, int P, int f, int block, const Sink& sink) {
     const int W = P * f;
     const int64_t items = (int64_t)R * P * P, plane = (int64_t)W * W;
     const float ff = (float)(f * f);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = (int64_t)blockIdx.x * block + threadIdx.x; i < items; i += (int64_t)gridDim.x * block) {
         const int ox = (int)(i % P);
         const int64_t t = i / P;
         const int oy = (int)(t % P), r = (int)(t / P);
-        float v[3];
+        float v[3][1] = {};
+        if (x) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float* xp = x + ((int64_t)r * 3 + c) * plane + (int64_t)oy * f * W + (int64_t)ox * f;
-            float s = 0.f;
-            for (int dy = 0; dy < f; ++dy)
-                for (int dx = 0; dx < f; ++dx) s += xp[(int64_t)dy * W + dx];
-            v[c] = s / ff;
-        }
-        put_pixel(o, r, oy, ox, P, v);
-    }
-}
-
-// ---------------------------------------------------------------- video frames (pooled sessions)
-// rendered rows -> [B,P,K*P,3] uint8 grid frames in one pass: up to three left panels [B or 1,3,P,P] converted as
-// grid_to_u8_kernel converts them, the f x f mean of x (the arithmetic of the frames kernels above) in the last panel.
-constexpr int kVideoLeft = 3;
-
-struct VideoPanels {
-    const float* x[kVideoLeft];
-    int64_t bstride[kVideoLeft];
-    int n;                                             // left panels; the pooled rows go into panel n
-};
-
-// one output pixel (b, oy, ox) of every panel.  Byte stores: a panel starts at a multiple of P*3 bytes, which is not a multiple of 4
-// for every P (P = 7), and adjacent lanes write adjacent 3-byte pixels, so the stores of a wave still fill whole lines.
-__device__ __forceinline__ void put_video_pixel(const VideoPanels& g, unsigned char* __restrict__ frames, int b, int oy, int ox, int P,
-                                                int swap_rb, const float (&v)[3]) {
-    const int64_t PP = (int64_t)P * P;
-    unsigned char* line = frames + ((int64_t)b * P + oy) * (int64_t)(g.n + 1) * P * 3 + (int64_t)ox * 3;
-#pragma unroll
-    for (int k = 0; k < kVideoLeft; ++k) {
-        if (k >= g.n) break;
-        if (g.x[k]) {
-            const float* s = g.x[k] + (int64_t)b * g.bstride[k] + (int64_t)oy * P + ox;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) line[swap_rb ? 2 - c : c] = to_u8(s[c * PP]);
-        }
-        line += (int64_t)P * 3;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) line[swap_rb ? 2 - c : c] = to_u8(v[c]);
-}
-
-// the lane scheme of sweep_frames_vec_kernel: four consecutive input columns of F rows per lane, 16-byte loads
-template <int F>
-__global__ __launch_bounds__(256) void video_frames_vec_kernel(const float* __restrict__ x, VideoPanels g,
-                                                               unsigned char* __restrict__ frames, int B, int P, int swap_rb) {
-    constexpr int NPIX = 4 / F;
-    const int W = P * F, Q = W / 4;
-    const int64_t items = (int64_t)B * P * Q, plane = (int64_t)W * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i % Q);
-        const int64_t t = i / Q;
-        const int oy = (int)(t % P), b = (int)(t / P);
-        float acc[3][NPIX];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-#pragma unroll
-            for (int p = 0; p < NPIX; ++p) acc[c][p] = 0.f;
-            const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * F * W + (int64_t)q * 4;
-#pragma unroll
-            for (int dy = 0; dy < F; ++dy) {
-                const float4 v = *reinterpret_cast<const float4*>(xp + (int64_t)dy * W);
-                const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[c][j / F] += e[j];
+            for (int c = 0; c < 3; ++c) {
+                const float* xp = x + ((int64_t)r * 3 + c) * plane + (int64_t)oy * f * W + (int64_t)ox * f;
+                float s = 0.f;
+                for (int dy = 0; dy < f; ++dy)
+                    for (int dx = 0; dx < f; ++dx) s += xp[(int64_t)dy * W + dx];
+                v[c][0] = s / ff;
             }
         }
-#pragma unroll
-        for (int p = 0; p < NPIX; ++p) {
-            const float v[3] = {acc[0][p] / (float)(F * F), acc[1][p] / (float)(F * F), acc[2][p] / (float)(F * F)};
-            put_video_pixel(g, frames, b, oy, q * NPIX + p, P, swap_rb, v);
-        }
+        sink(r, oy, ox, v);
     }
 }
 
-// dword path: one output pixel per lane, the same order of additions
-__global__ __launch_bounds__(256) void video_frames_scalar_kernel(const float* __restrict__ x, VideoPanels g,
-                                                                  unsigned char* __restrict__ frames, int B, int P, int f, int swap_rb) {
+// The launch of a walk: 16-byte lanes where a row of x is a whole number of them and x starts on one, a grid-stride loop over at
+// most 65536 blocks of kWalkBlock threads (the kernels read it as blockDim.x), the kernel picked by f.  The kernels take (x, R, P, tail...), the dword one (x, R, P, f, tail...).
+template <class... T>
+static void launch_walk(void (*vec1)(const float*, int, int, T...), void (*vec2)(const float*, int, int, T...),
+                        void (*vec4)(const float*, int, int, T...), void (*scalar)(const float*, int, int, int, T...), const float* x,
+                        int R, int P, int f, void* stream, T... tail) {
     const int W = P * f;
-    const int64_t items = (int64_t)B * P * P, plane = (int64_t)W * W;
-    const float ff = (float)(f * f);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
-        const int ox = (int)(i % P);
-        const int64_t t = i / P;
-        const int oy = (int)(t % P), b = (int)(t / P);
-        float v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * f * W + (int64_t)ox * f;
-            float s = 0.f;
-            for (int dy = 0; dy < f; ++dy)
-                for (int dx = 0; dx < f; ++dx) s += xp[(int64_t)dy * W + dx];
-            v[c] = s / ff;
-        }
-        put_video_pixel(g, frames, b, oy, ox, P, swap_rb, v);
-    }
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    const int64_t items = vec ? (int64_t)R * P * (W / 4) : (int64_t)R * P * P;
+    int64_t blocks = (items + kWalkBlock - 1) / kWalkBlock;
+    if (blocks > 65536) blocks = 65536;
+    const dim3 grid((unsigned)blocks), block(kWalkBlock);
+    hipStream_t st = as_stream(stream);
+    if (!vec) hipLaunchKernelGGL(scalar, grid, block, 0, st, x, R, P, f, tail...);
+    else hipLaunchKernelGGL(f == 1 ? vec1 : f == 2 ? vec2 : vec4, grid, block, 0, st, x, R, P, tail...);
+}
+#define SGDFR_WALK_KERNELS(name) name##_vec_kernel<1>, name##_vec_kernel<2>, name##_vec_kernel<4>, name##_scalar_kernel
+
+// sweep frames: the walk into put_pixel
+template <int F>
+__global__ __launch_bounds__(kWalkBlock) void sweep_frames_vec_kernel(const float* __restrict__ x, int R, int P, FramesOut o) {
+    pooled_walk_vec<F>(x, R, P, blockDim.x, [=](int r, int oy, int ox0, const float (&v)[3][4 / F]) { put_pixels(o, r, oy, ox0, P, v); });
 }
 
-// ---------------------------------------------------------------- video frames from typed, indexed panels
-// The pass above with left panels that are float32 planar [rows,3,P,P] or uint8 interleaved [rows,P,P,3] (the alignment crop's own
-// bytes), each read at row index[b] of its table (clamped into the table), at row b, or at its only row; x may be absent.
+__global__ __launch_bounds__(kWalkBlock) void sweep_frames_scalar_kernel(const float* __restrict__ x, int R, int P, int f, FramesOut o) {
+    pooled_walk_scalar(x, R, P, f, blockDim.x, [=](int r, int oy, int ox0, const float (&v)[3][1]) { put_pixels(o, r, oy, ox0, P, v); });
+}
+
+// ---------------------------------------------------------------- video frames
+// rendered rows -> [B,P,K*P,3] uint8 grid frames in one pass: up to three left panels converted as grid_to_u8_kernel converts them,
+// the f x f mean of x (the walk above) in the last panel.  A left panel is float32 planar [rows,3,P,P] or uint8 interleaved
+// [rows,P,P,3] (the alignment crop's own bytes), read at row index[b] of its table (clamped into the table), at row b, or at its only
+// row; x may be absent.  Both video entries launch these kernels: sgdfr_video_frames_f32 describes its float panels as such tables.
+constexpr int kVideoLeft = 3;
+
 struct PxPanels {
     const void* data[kVideoLeft];
     const int* index[kVideoLeft];
@@ -408,62 +377,23 @@ __device__ __forceinline__ void put_px_pixels(const PxPanels& g, unsigned char* 
     }
 }
 
-// the lane scheme of video_frames_vec_kernel; without x (F = 1) a lane converts four pixels of every left panel and stops there
+// the walk into put_px_pixels; without x (F = 1) a lane converts four pixels of every left panel and stops there.  The sink lives
+// inside the kernel and refers to its arguments (see the walk's header for why not a copy)
 template <int F>
-__global__ __launch_bounds__(256) void video_px_vec_kernel(const float* __restrict__ x, PxPanels g, unsigned char* __restrict__ frames,
-                                                           int B, int P, int swap_rb) {
-    constexpr int NPIX = 4 / F;
-    const int W = P * F, Q = W / 4;
-    const int64_t items = (int64_t)B * P * Q, plane = (int64_t)W * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i % Q);
-        const int64_t t = i / Q;
-        const int oy = (int)(t % P), b = (int)(t / P);
-        float v[3][NPIX] = {};
-        if (x) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-#pragma unroll
-                for (int p = 0; p < NPIX; ++p) v[c][p] = 0.f;
-                const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * F * W + (int64_t)q * 4;
-#pragma unroll
-                for (int dy = 0; dy < F; ++dy) {
-                    const float4 e4 = *reinterpret_cast<const float4*>(xp + (int64_t)dy * W);
-                    const float e[4] = {e4.x, e4.y, e4.z, e4.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[c][j / F] += e[j];
-                }
-#pragma unroll
-                for (int p = 0; p < NPIX; ++p) v[c][p] = v[c][p] / (float)(F * F);
-            }
-        }
-        put_px_pixels<NPIX>(g, frames, b, oy, q * NPIX, P, swap_rb, x != nullptr, v);
-    }
+__global__ __launch_bounds__(kWalkBlock) void video_px_vec_kernel(const float* __restrict__ x, int B, int P, PxPanels g,
+                                                           unsigned char* __restrict__ frames, int swap_rb) {
+    const bool last = x != nullptr;
+    pooled_walk_vec<F>(x, B, P, blockDim.x, [&](int b, int oy, int ox0, const float (&v)[3][4 / F]) {
+        put_px_pixels<4 / F>(g, frames, b, oy, ox0, P, swap_rb, last, v);
+    });
 }
 
-// dword path: one output pixel per lane, the same order of additions
-__global__ __launch_bounds__(256) void video_px_scalar_kernel(const float* __restrict__ x, PxPanels g, unsigned char* __restrict__ frames,
-                                                              int B, int P, int f, int swap_rb) {
-    const int W = P * f;
-    const int64_t items = (int64_t)B * P * P, plane = (int64_t)W * W;
-    const float ff = (float)(f * f);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
-        const int ox = (int)(i % P);
-        const int64_t t = i / P;
-        const int oy = (int)(t % P), b = (int)(t / P);
-        float v[3][1] = {};
-        if (x) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* xp = x + ((int64_t)b * 3 + c) * plane + (int64_t)oy * f * W + (int64_t)ox * f;
-                float s = 0.f;
-                for (int dy = 0; dy < f; ++dy)
-                    for (int dx = 0; dx < f; ++dx) s += xp[(int64_t)dy * W + dx];
-                v[c][0] = s / ff;
-            }
-        }
-        put_px_pixels<1>(g, frames, b, oy, ox, P, swap_rb, x != nullptr, v);
-    }
+__global__ __launch_bounds__(kWalkBlock) void video_px_scalar_kernel(const float* __restrict__ x, int B, int P, int f, PxPanels g,
+                                                              unsigned char* __restrict__ frames, int swap_rb) {
+    const bool last = x != nullptr;
+    pooled_walk_scalar(x, B, P, f, blockDim.x, [&](int b, int oy, int ox0, const float (&v)[3][1]) {
+        put_px_pixels<1>(g, frames, b, oy, ox0, P, swap_rb, last, v);
+    });
 }
 
 static int gather_table(const char* who, const sgdfr_direction* table, int D, const int* dirs, int K, int pose_dim, int exp_dim,
@@ -575,46 +505,28 @@ extern "C" int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const
     if (R == 0 || (!pooled && !bordered && !frames)) return 0;
     SGDFR_REQUIRE(x, "sweep_frames: null input");
     FramesOut o{pooled, bordered, frames, src, src_bstride, is_start, panels};
-    const int W = P * f;
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int64_t items = vec ? (int64_t)R * P * (W / 4) : (int64_t)R * P * P;
-    int64_t blocks = (items + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    const dim3 grid((unsigned)blocks), block(256);
-    hipStream_t st = as_stream(stream);
-    if (!vec) hipLaunchKernelGGL(sweep_frames_scalar_kernel, grid, block, 0, st, x, o, R, P, f);
-    else if (f == 1) hipLaunchKernelGGL(sweep_frames_vec_kernel<1>, grid, block, 0, st, x, o, R, P);
-    else if (f == 2) hipLaunchKernelGGL(sweep_frames_vec_kernel<2>, grid, block, 0, st, x, o, R, P);
-    else hipLaunchKernelGGL(sweep_frames_vec_kernel<4>, grid, block, 0, st, x, o, R, P);
+    launch_walk(SGDFR_WALK_KERNELS(sweep_frames), x, R, P, f, stream, o);
     return check_launch("sweep_frames");
 }
 
+// the float panels of this entry as the tables of the next: stride 0 is a table of one row, stride 3 * P * P one of B rows
 extern "C" int sgdfr_video_frames_f32(const float* x, int B, int P, int f, const float* const* panels, const int64_t* bstrides, int n_left,
                                       unsigned char* frames, int swap_rb, void* stream) {
     SGDFR_REQUIRE(f == 1 || f == 2 || f == 4, "video_frames: the pooling factor must be 1, 2 or 4 (256, 512, 1024 generators), got %d", f);
     SGDFR_REQUIRE(B >= 0 && P >= 1 && P <= 8192, "video_frames: bad shape B=%d P=%d", B, P);
     SGDFR_REQUIRE(n_left >= 0 && n_left <= kVideoLeft, "video_frames: %d left panels (0..%d)", n_left, kVideoLeft);
     SGDFR_REQUIRE(n_left == 0 || (panels && bstrides), "video_frames: left panels without their pointer and stride arrays");
-    VideoPanels g{};
+    PxPanels g{};
     g.n = n_left;
     for (int k = 0; k < n_left; ++k) {
         SGDFR_REQUIRE(bstrides[k] == 0 || bstrides[k] == (int64_t)3 * P * P, "video_frames: panel %d is one image (stride 0) or one per row", k);
-        g.x[k] = panels[k];
-        g.bstride[k] = bstrides[k];
+        g.data[k] = panels[k];
+        g.kind[k] = SGDFR_PANEL_F32;
+        g.rows[k] = bstrides[k] == 0 ? 1 : B;
     }
     if (B == 0) return 0;
     SGDFR_REQUIRE(x && frames, "video_frames: null pointer");
-    const int W = P * f;
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int64_t items = vec ? (int64_t)B * P * (W / 4) : (int64_t)B * P * P;
-    int64_t blocks = (items + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    const dim3 grid((unsigned)blocks), block(256);
-    hipStream_t st = as_stream(stream);
-    if (!vec) hipLaunchKernelGGL(video_frames_scalar_kernel, grid, block, 0, st, x, g, frames, B, P, f, swap_rb);
-    else if (f == 1) hipLaunchKernelGGL(video_frames_vec_kernel<1>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
-    else if (f == 2) hipLaunchKernelGGL(video_frames_vec_kernel<2>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
-    else hipLaunchKernelGGL(video_frames_vec_kernel<4>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    launch_walk(SGDFR_WALK_KERNELS(video_px), x, B, P, f, stream, g, frames, swap_rb);
     return check_launch("video_frames");
 }
 
@@ -643,16 +555,6 @@ extern "C" int sgdfr_video_frames_px(const float* x, int B, int P, int f, const 
     if (B == 0 || !any) return 0;
     SGDFR_REQUIRE(frames, "video_frames_px: null frames pointer");
     if (!x) f = 1;                                      // nothing to pool: the lanes walk the output pixels
-    const int W = P * f;
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int64_t items = vec ? (int64_t)B * P * (W / 4) : (int64_t)B * P * P;
-    int64_t blocks = (items + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    const dim3 grid((unsigned)blocks), block(256);
-    hipStream_t st = as_stream(stream);
-    if (!vec) hipLaunchKernelGGL(video_px_scalar_kernel, grid, block, 0, st, x, g, frames, B, P, f, swap_rb);
-    else if (f == 1) hipLaunchKernelGGL(video_px_vec_kernel<1>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
-    else if (f == 2) hipLaunchKernelGGL(video_px_vec_kernel<2>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
-    else hipLaunchKernelGGL(video_px_vec_kernel<4>, grid, block, 0, st, x, g, frames, B, P, swap_rb);
+    launch_walk(SGDFR_WALK_KERNELS(video_px), x, B, P, f, stream, g, frames, swap_rb);
     return check_launch("video_frames_px");
 }

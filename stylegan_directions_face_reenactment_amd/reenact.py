@@ -35,6 +35,51 @@ def images_to_uint8(images):
     return y
 
 
+def _left_panel(p, B, tail, indexed, bad_shape, bad_rows):
+    """One left panel of a frames launch, on the device already: None stays None (skipped: `out` keeps it), [*tail] becomes
+    [1,*tail]; the shape behind the rows must be `tail`, the rows 1 (shown in every frame) or B unless the panel is `indexed`.
+    bad_shape / bad_rows are the caller's error texts with one %s for the shape found.  -> the contiguous panel."""
+    if p is None:
+        return None
+    p = p if p.ndim == 4 else p.unsqueeze(0)
+    if p.ndim != 4 or tuple(p.shape[1:]) != tuple(tail) or p.shape[0] < 1:
+        raise RuntimeError(bad_shape % (tuple(p.shape),))
+    if not indexed and p.shape[0] not in (1, B):
+        raise RuntimeError(bad_rows % (tuple(p.shape),))
+    return p.contiguous()
+
+
+def _float_panel_args(xs, B):
+    """The pointer and batch-stride arrays the float entries take for panels checked by _left_panel (NULL = skipped, stride 0 = one
+    row shown in every frame)."""
+    n = max(len(xs), 1)
+    ptrs = (ctypes.c_void_p * n)(*[None if p is None else p.data_ptr() for p in xs])
+    strides = (ctypes.c_int64 * n)(*[0 if (p is None or (p.shape[0] == 1 and B > 1)) else p.numel() // p.shape[0] for p in xs])
+    return ptrs, strides
+
+
+def _frames_out(who, out, shape, device, skipped):
+    """The uint8 frames tensor [B,H,K*W,3] of a frames launch: `out` checked, or a new one -- which `skipped` panels rule out."""
+    if out is None:
+        if skipped:
+            raise RuntimeError('%s: a skipped panel needs the `out` tensor that already holds it' % who)
+        return torch.empty(shape, device=device, dtype=torch.uint8)
+    if not torch.is_tensor(out) or tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+        raise RuntimeError('%s: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % ((who,) + tuple(shape[:3])))
+    return out
+
+
+def _square_rgb(who, x, P, default_P=True):
+    """x [B,3,S,S] float32 on the device -> (x contiguous, B, P, f): P defaults to 256, or S below that; f = S / P (_pool_factor)."""
+    N.require_device(x)
+    x = N.f32c(x)
+    if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise RuntimeError('%s: expected square RGB images [B,3,S,S], got %s' % (who, tuple(x.shape)))
+    if P is None and default_P:
+        P = min(x.shape[2], 256)
+    return x, x.shape[0], P, _pool_factor(x.shape[2], P)
+
+
 def grid_frames_uint8(panels, swap_rb=False, out=None):
     """Side-by-side video frames for a batch: panels = list of [B,3,H,W] or [1,3,H,W] (shown in every frame) fp32
     images in [-1,1] -> [B,H,K*W,3] uint8.  One launch for what the reference does per frame with
@@ -43,33 +88,19 @@ def grid_frames_uint8(panels, swap_rb=False, out=None):
     already wrote it there: Generator.forward(image_out=U8Target(out, panel)))."""
     if not 1 <= len(panels) <= 4:
         raise RuntimeError('grid_frames_uint8 takes 1..4 panels, got %d' % len(panels))
-    xs = []
-    for x in panels:
-        if x is None:
-            xs.append(None)
-            continue
-        N.require_device(x)
-        xs.append(N.f32c(x if x.ndim == 4 else x.unsqueeze(0)))
-    given = [x for x in xs if x is not None]
-    if not given and out is None:
-        raise RuntimeError('grid_frames_uint8: nothing to write')
-    if given:
-        B = max(x.shape[0] for x in given) if out is None else out.shape[0]
-        _, C, H, W = given[0].shape
-    else:
+    given = [x for x in panels if x is not None]
+    if not given:
+        if out is None:
+            raise RuntimeError('grid_frames_uint8: nothing to write')
         return out
-    for x in given:
-        if x.shape[1:] != (3, H, W) or x.shape[0] not in (1, B):
-            raise RuntimeError('grid panels must be [B or 1,3,%d,%d], got %s' % (H, W, tuple(x.shape)))
+    N.require_device(*given)
+    H, W = given[0].shape[-2:]
+    B = out.shape[0] if out is not None else max(x.shape[0] if x.ndim == 4 else 1 for x in given)
+    bad = 'grid panels must be [B or 1,3,%d,%d], got %%s' % (H, W)
+    xs = [_left_panel(x, B, (3, H, W), False, bad, bad) for x in panels]
     K = len(xs)
-    if any(x is None for x in xs) and out is None:
-        raise RuntimeError('grid_frames_uint8: a skipped panel needs the `out` tensor that already holds it')
-    ptrs = (ctypes.c_void_p * K)(*[None if x is None else x.data_ptr() for x in xs])
-    strides = (ctypes.c_int64 * K)(*[0 if (x is None or (x.shape[0] == 1 and B > 1)) else 3 * H * W for x in xs])
-    if out is None:
-        out = torch.empty(B, H, K * W, 3, device=given[0].device, dtype=torch.uint8)
-    elif tuple(out.shape) != (B, H, K * W, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-        raise RuntimeError('grid_frames_uint8: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (B, H, K * W))
+    out = _frames_out('grid_frames_uint8', out, (B, H, K * W, 3), given[0].device, len(given) < K)
+    ptrs, strides = _float_panel_args(xs, B)
     N.call('sgdfr_grid_to_u8_f32', ptrs, strides, K, N.ptr(out), B, H, W, int(bool(swap_rb)), N.stream())
     return out
 
@@ -86,11 +117,7 @@ def _pool_factor(size, pool_to):
 def pool_images(x, P, as_uint8=False):
     """x [B,3,P*f,P*f] float32 -> the f x f mean [B,3,P,P] float32, or with as_uint8 its [B,P,P,3] uint8 frames: one
     ``sgdfr_sweep_frames_f32`` launch (AdaptiveAvgPool2d((P,P)) for f = 1, 2, 4, as generic.generate_image pools above 256)."""
-    N.require_device(x)
-    x = N.f32c(x)
-    if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-        raise RuntimeError('pool_images: expected square RGB images [B,3,S,S], got %s' % (tuple(x.shape),))
-    B, f = x.shape[0], _pool_factor(x.shape[2], P)
+    x, B, P, f = _square_rgb('pool_images', x, P, default_P=False)
     y = torch.empty((B, P, P, 3) if as_uint8 else (B, 3, P, P), device=x.device, dtype=torch.uint8 if as_uint8 else torch.float32)
     N.call('sgdfr_sweep_frames_f32', N.ptr(x), B, P, f, None, None, 0, None if as_uint8 else N.ptr(y), None,
            N.ptr(y) if as_uint8 else None, 1, N.stream())
@@ -102,36 +129,15 @@ def video_frames_uint8(x, panels=(), P=None, swap_rb=False, out=None):
     256, or the side of x below that) is pooled f x f and placed to the right of up to three left `panels` ([B or 1,3,P,P] float32;
     None = leave that panel of `out` as it is) -> [B,P,K*P,3] uint8, K = len(panels) + 1.  The bytes are those of
     pool_images(x, P) -> grid_frames_uint8(panels + [pooled]) without the float intermediate."""
-    N.require_device(x)
-    x = N.f32c(x)
-    if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-        raise RuntimeError('video_frames_uint8: expected square RGB images [B,3,S,S], got %s' % (tuple(x.shape),))
-    B, S = x.shape[0], x.shape[2]
-    if P is None:
-        P = min(S, 256)
-    f = _pool_factor(S, P)
+    who = 'video_frames_uint8'
+    x, B, P, f = _square_rgb(who, x, P)
     if len(panels) > 3:
-        raise RuntimeError('video_frames_uint8 takes up to 3 left panels, got %d' % len(panels))
-    xs = []
-    for p in panels:
-        if p is None:
-            xs.append(None)
-            continue
-        N.require_device(p)
-        p = N.f32c(p if p.ndim == 4 else p.unsqueeze(0))
-        if tuple(p.shape[1:]) != (3, P, P) or p.shape[0] not in (1, B):
-            raise RuntimeError('video_frames_uint8: left panels must be [1 or %d,3,%d,%d], got %s' % (B, P, P, tuple(p.shape)))
-        xs.append(p)
-    K = len(xs) + 1
-    if out is None:
-        if any(p is None for p in xs):
-            raise RuntimeError('video_frames_uint8: a skipped panel needs the `out` tensor that already holds it')
-        out = torch.empty(B, P, K * P, 3, device=x.device, dtype=torch.uint8)
-    elif tuple(out.shape) != (B, P, K * P, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-        raise RuntimeError('video_frames_uint8: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (B, P, K * P))
-    n = max(len(xs), 1)
-    ptrs = (ctypes.c_void_p * n)(*[None if p is None else p.data_ptr() for p in xs])
-    strides = (ctypes.c_int64 * n)(*[0 if (p is None or (p.shape[0] == 1 and B > 1)) else 3 * P * P for p in xs])
+        raise RuntimeError('%s takes up to 3 left panels, got %d' % (who, len(panels)))
+    N.require_device(*panels)
+    bad = '%s: left panels must be [1 or %d,3,%d,%d], got %%s' % (who, B, P, P)
+    xs = [_left_panel(p, B, (3, P, P), False, bad, bad) for p in panels]
+    out = _frames_out(who, out, (B, P, (len(xs) + 1) * P, 3), x.device, any(p is None for p in xs))
+    ptrs, strides = _float_panel_args(xs, B)
     N.call('sgdfr_video_frames_f32', N.ptr(x), B, P, f, ptrs, strides, len(xs), N.ptr(out), int(bool(swap_rb)), N.stream())
     return out
 
@@ -170,14 +176,7 @@ def video_frames_px(x, panels, P=None, swap_rb=False, out=None, index=None):
     if x is not None:
         if not torch.is_tensor(x) or x.dtype != torch.float32:
             raise RuntimeError('%s: x must be a float32 device tensor or None, got %s' % (who, x.dtype if torch.is_tensor(x) else type(x)))
-        N.require_device(x)
-        x = N.f32c(x)
-        if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-            raise RuntimeError('%s: expected square RGB images [B,3,S,S], got %s' % (who, tuple(x.shape)))
-        B, S = x.shape[0], x.shape[2]
-        if P is None:
-            P = min(S, 256)
-        f = _pool_factor(S, P)
+        x, B, P, f = _square_rgb(who, x, P)
         device = x.device
     else:
         if out is None or not torch.is_tensor(out) or out.ndim != 4:
@@ -210,27 +209,17 @@ def video_frames_px(x, panels, P=None, swap_rb=False, out=None, index=None):
         for t in (p, ix):
             if t is not None and not t.is_cuda:
                 raise RuntimeError('expected a GPU (HIP) tensor, got device %s: this package has no CPU path' % t.device)
-        p = p if p.ndim == 4 else p.unsqueeze(0)
-        if p.ndim != 4 or tuple(p.shape[1:]) != tail or p.shape[0] < 1:
-            raise RuntimeError('%s: left panels must be [rows,%d,%d,%d] (%s), got %s'
-                               % (who, tail[0], tail[1], tail[2], str(p.dtype).replace('torch.', ''), tuple(p.shape)))
-        p = p.contiguous()
+        p = _left_panel(p, B, tail, ix is not None,
+                        '%s: left panels must be [rows,%d,%d,%d] (%s), got %%s' % ((who,) + tail + (str(p.dtype).replace('torch.', ''),)),
+                        '%s: left panels without an index must have 1 or %d rows, got %%s' % (who, B))
         if ix is not None:
             if tuple(ix.shape) != (B,) or not ix.is_contiguous():
                 raise RuntimeError('%s: the index of panel %d must be a contiguous [%d] tensor, got %s' % (who, k, B, tuple(ix.shape)))
             keep.append(ix)
-        elif p.shape[0] not in (1, B):
-            raise RuntimeError('%s: left panels without an index must have 1 or %d rows, got %s' % (who, B, tuple(p.shape)))
         keep.append(p)
         descs[k].data, descs[k].index = p.data_ptr(), (None if ix is None else ix.data_ptr())
         descs[k].kind, descs[k].rows = kind, p.shape[0]
-    if out is None:
-        if any(p is None for p in panels):
-            raise RuntimeError('%s: a skipped panel needs the `out` tensor that already holds it' % who)
-        out = torch.empty(B, P, K * P, 3, device=device, dtype=torch.uint8)
-    elif not torch.is_tensor(out) or tuple(out.shape) != (B, P, K * P, 3) or out.dtype != torch.uint8 or not out.is_cuda \
-            or not out.is_contiguous():
-        raise RuntimeError('%s: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (who, B, P, K * P))
+    out = _frames_out(who, out, (B, P, K * P, 3), device, any(p is None for p in panels))
     N.call('sgdfr_video_frames_px', N.ptr(x), B, P, f, descs, len(panels), N.ptr(out), int(bool(swap_rb)), N.stream())
     return out
 
@@ -581,12 +570,7 @@ class ReenactmentSession:
         if as_bytes and (H != W or tuple(target_images.shape) != (n, H, W, 3)):
             raise RuntimeError('video_frames: uint8 target crops must be [%d,%d,%d,3] next to a square source panel, got %s'
                                % (n, H, W, tuple(target_images.shape)))
-        if out is None:
-            video = torch.empty(n, H, 3 * W, 3, device=shift_vectors.device, dtype=torch.uint8)
-        elif tuple(out.shape) != (n, H, 3 * W, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise RuntimeError('video_frames: out must be a contiguous uint8 [%d,%d,%d,3] device tensor' % (n, H, 3 * W))
-        else:
-            video = out
+        video = _frames_out('video_frames', out, (n, H, 3 * W, 3), shift_vectors.device, False)
         if self.pool_to is not None:
             if (H, W) != (self.pool_to, self.pool_to):
                 raise RuntimeError('video_frames: this session pools to %d, the source panel is %d x %d' % (self.pool_to, H, W))
@@ -834,23 +818,57 @@ class Reenactor:
         return {'crop': src.crop, 'x': src.x, 'source_code': src.code, 'inverted': src.inverted, 'params': src.params,
                 'angles': src.angles, 'loss': src.loss}
 
+    def _head_chain(self, frames):
+        """One chunk of target frames through the heads: _preprocess -> detect_landmarks(input_range='gan') on the crops ->
+        shape_params(boxes=, has_face=) -> (crop uint8, x float, params, angles, has_face on the frame, valid crop, has_face on the
+        crop).  `analyse` and `target_shift_vectors` chunk by `batch` and call this, so their bits agree."""
+        from .face_detector import detect_landmarks
+        from .train_step import shape_params
+        crop, x, has_frame, valid = _preprocess(self.det, self.fan, frames)
+        _, boxes, has = detect_landmarks(self.det, self.fan, x, input_range='gan')
+        params, angles = shape_params(self.det, self.fan, self.E, x, boxes=boxes, has_face=has)
+        return crop, x, params, angles, has_frame, valid, has
+
+    @staticmethod
+    def _check_policy(who, on_fail, output):
+        """on_fail and output of the three reenact methods: refused before anything else is looked at."""
+        if on_fail not in ON_FAIL:
+            raise RuntimeError('%s: on_fail must be one of %s, got %r' % (who, ', '.join(ON_FAIL), on_fail))
+        if output not in OUTPUTS:
+            raise RuntimeError('%s: output must be one of %s, got %r' % (who, ', '.join(OUTPUTS), output))
+
+    @staticmethod
+    def _check_valid(who, valid, n):
+        """The caller's `valid` mask of the three reenact methods, once the rows are known to be n: None or a bool tensor [n]."""
+        if valid is not None and (not torch.is_tensor(valid) or valid.dtype != torch.bool or tuple(valid.shape) != (n,)):
+            raise RuntimeError('%s: valid must be a bool tensor [%d]' % (who, n))
+
+    def _apply_on_fail(self, who, sv, ok, on_fail):
+        """The shift vectors a call renders: sv [N,D] (reenact, reenact_analysed: 'hold' uses and updates the Reenactor's carry) or
+        [S,N,D] (reenact_many: every source holds from an empty carry) under the policy for the rows whose ok [N] is False."""
+        if on_fail == 'raise':
+            _raise_failed_rows(who, ok)
+            return sv
+        if on_fail == 'source':
+            return torch.where(ok.unsqueeze(-1), sv, torch.zeros((), dtype=sv.dtype, device=sv.device))
+        if sv.ndim == 3:
+            return hold_failed_rows_many(sv, ok)
+        sv, self._carry, self._carry_valid = hold_failed_rows(sv, ok, self._carry, self._carry_valid)
+        return sv
+
     @torch.no_grad()
     def analyse(self, frames):
         """The head chain of `target_shift_vectors` for frames [N,H,W,3] uint8 on the device, up to but not including make_shift, so
         without any source (it works before set_source): `batch` frames at a time preprocess_frames -> detect_landmarks(input_range=
         'gan') on the crops -> shape_params(boxes=, has_face=).  Returns a `TargetAnalysis`; the float crops live only inside a chunk.
         No host synchronisation of its own."""
-        from .face_detector import detect_landmarks
-        from .train_step import shape_params
         frames = _device_frames(frames, 'analyse')
         if frames.ndim != 4 or frames.shape[0] < 1:
             raise RuntimeError('analyse: expected frames [N,H,W,3], got %s' % (tuple(frames.shape),))
         frames = frames.contiguous()
         crops, angles, oks, valids, params = [], [], [], [], {}
         for lo in range(0, frames.shape[0], self.batch):
-            crop, x, has_frame, valid = _preprocess(self.det, self.fan, frames[lo:lo + self.batch])
-            _, boxes, has = detect_landmarks(self.det, self.fan, x, input_range='gan')
-            p, ang = shape_params(self.det, self.fan, self.E, x, boxes=boxes, has_face=has)
+            crop, x, p, ang, has_frame, valid, has = self._head_chain(frames[lo:lo + self.batch])
             for k, v in p.items():
                 params.setdefault(k, []).append(v)
             crops.append(crop)
@@ -866,16 +884,12 @@ class Reenactor:
         face_detector.detect_landmarks(input_range='gan') on the crops -> shape_params(boxes=, has_face=) -> shifts.make_shift
         against the source's rows.  Returns (x [N,3,256,256] the target crops, sv [N,D] before any policy, ok [N] bool =
         has_face on the frame & valid crop & has_face on the crop)."""
-        from .face_detector import detect_landmarks
-        from .train_step import shape_params
         xs, svs, oks = [], [], []
         for lo in range(0, frames.shape[0], self.batch):
-            _, x, ok = preprocess_frames(self.det, self.fan, frames[lo:lo + self.batch])
-            _, boxes, has = detect_landmarks(self.det, self.fan, x, input_range='gan')
-            params, angles = shape_params(self.det, self.fan, self.E, x, boxes=boxes, has_face=has)
+            _, x, params, angles, has_frame, valid, has = self._head_chain(frames[lo:lo + self.batch])
             svs.append(self.shifts.make_shift(self.source_angles, angles, self.source_params, params))
             xs.append(x)
-            oks.append(ok & has)
+            oks.append(has_frame & valid & has)
         return torch.cat(xs, 0), torch.cat(svs, 0), torch.cat(oks, 0)
 
     @torch.no_grad()
@@ -893,29 +907,17 @@ class Reenactor:
         range check one chunk behind its launches, as it always does.  The target crops of a 'video' call stay on the device until
         it returns (0.79 MB per frame): hand a long video over in segments, the hold carry spans the calls -- or `analyse` it once
         (0.20 MB per frame, uint8) and render from that with `reenact_analysed` / `reenact_many`."""
-        if on_fail not in ON_FAIL:
-            raise RuntimeError('reenact: on_fail must be one of %s, got %r' % (', '.join(ON_FAIL), on_fail))
-        if output not in OUTPUTS:
-            raise RuntimeError('reenact: output must be one of %s, got %r' % (', '.join(OUTPUTS), output))
+        self._check_policy('reenact', on_fail, output)
         frames = _device_frames(frames, 'reenact')
         if self.session is None:
             raise RuntimeError('reenact: no source yet (call set_source first)')
         if frames.ndim != 4 or frames.shape[0] < 1:
             raise RuntimeError('reenact: expected frames [N,H,W,3], got %s' % (tuple(frames.shape),))
-        n = frames.shape[0]
-        if valid is not None:
-            if not torch.is_tensor(valid) or valid.dtype != torch.bool or tuple(valid.shape) != (n,):
-                raise RuntimeError('reenact: valid must be a bool tensor [%d]' % n)
-            valid = valid.to(frames.device)
+        self._check_valid('reenact', valid, frames.shape[0])
         x, sv, ok = self.target_shift_vectors(frames.contiguous())
         if valid is not None:
-            ok = ok & valid
-        if on_fail == 'raise':
-            _raise_failed_rows('reenact', ok)
-        elif on_fail == 'hold':
-            sv, self._carry, self._carry_valid = hold_failed_rows(sv, ok, self._carry, self._carry_valid)
-        else:
-            sv = torch.where(ok.unsqueeze(1), sv, torch.zeros_like(sv))
+            ok = ok & valid.to(frames.device)
+        sv = self._apply_on_fail('reenact', sv, ok, on_fail)
         if output == 'video':
             out = self.session.video_frames(self.source_x, x, sv, swap_rb=True)
         else:
@@ -924,15 +926,11 @@ class Reenactor:
 
     def _check_analysed(self, who, analysis, valid, on_fail, output):
         """The argument checks shared by reenact_analysed and reenact_many -> (ok [N] with the caller's mask folded in)."""
-        if on_fail not in ON_FAIL:
-            raise RuntimeError('%s: on_fail must be one of %s, got %r' % (who, ', '.join(ON_FAIL), on_fail))
-        if output not in OUTPUTS:
-            raise RuntimeError('%s: output must be one of %s, got %r' % (who, ', '.join(OUTPUTS), output))
+        self._check_policy(who, on_fail, output)
         if not isinstance(analysis, TargetAnalysis):
             raise RuntimeError('%s: expected the TargetAnalysis of analyse(frames), got %s' % (who, type(analysis)))
         n = len(analysis)
-        if valid is not None and (not torch.is_tensor(valid) or valid.dtype != torch.bool or tuple(valid.shape) != (n,)):
-            raise RuntimeError('%s: valid must be a bool tensor [%d]' % (who, n))
+        self._check_valid(who, valid, n)
         N.require_device(analysis.crops, dtype=torch.uint8)
         N.require_device(analysis.angles, *analysis.params.values())
         if n < 1 or tuple(analysis.crops.shape[1:]) != (256, 256, 3):
@@ -954,12 +952,7 @@ class Reenactor:
         if self.session is None:
             raise RuntimeError('reenact_analysed: no source yet (call set_source or use_source first)')
         sv = self.shifts.make_shift(self.source_angles, analysis.angles, self.source_params, analysis.params)
-        if on_fail == 'raise':
-            _raise_failed_rows('reenact_analysed', ok)
-        elif on_fail == 'hold':
-            sv, self._carry, self._carry_valid = hold_failed_rows(sv, ok, self._carry, self._carry_valid)
-        else:
-            sv = torch.where(ok.unsqueeze(1), sv, torch.zeros_like(sv))
+        sv = self._apply_on_fail('reenact_analysed', sv, ok, on_fail)
         if output == 'video':
             out = self.session.video_frames(self.source_x, analysis.crops, sv, swap_rb=True)
             self._finish_target_panel(out, analysis)
@@ -988,12 +981,7 @@ class Reenactor:
         sources = self._check_sources('reenact_many', sources)
         ok = self._check_analysed('reenact_many', analysis, valid, on_fail, output)
         sv = torch.stack([self.shifts.make_shift(s.angles, analysis.angles, s.params, analysis.params) for s in sources], 0)
-        if on_fail == 'raise':
-            _raise_failed_rows('reenact_many', ok)
-        elif on_fail == 'hold':
-            sv = hold_failed_rows_many(sv, ok)
-        else:
-            sv = torch.where(ok.view(1, -1, 1), sv, torch.zeros((), dtype=sv.dtype, device=sv.device))
+        sv = self._apply_on_fail('reenact_many', sv, ok, on_fail)
         n = len(analysis)
         out = torch.empty(len(sources), n, 256, 768 if output == 'video' else 256, 3, device=sv.device, dtype=torch.uint8)
         for s, src in enumerate(sources):

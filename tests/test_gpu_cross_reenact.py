@@ -3,7 +3,8 @@ reenact.video_frames_px), and Reenactor.analyse / reenact_analysed / reenact_man
 tests/test_gpu_reenactor.py (synthetic weights in every network).
 
 Bars.  Everything here is the existing launches on the same numbers in the same chunks, so every comparison is for equal bytes / equal
-bits: the new launch against video_frames_uint8 on materialised float panels, the analysis against the head chain written out from
+bits: the px launch against pool_images -> grid_frames_uint8 on materialised float panels (util.composed: both video entries run the
+px kernels, so video_frames_uint8 would be no witness), the analysis against the head chain written out from
 public calls, reenact_analysed against reenact, reenact_many against set_source + reenact per source, cross_metrics against
 evaluation_metrics written out.  Every test prints the figures it asserts on."""
 import pytest
@@ -11,7 +12,7 @@ import torch
 
 import cross_reenact_restatement as X
 from test_gpu_reenactor import Rig, bits, direction_matrix
-from util import S, SEED, hip_generator
+from util import S, SEED, composed, hip_generator
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +47,10 @@ def fill_bytes(B, P, K):
 @pytest.mark.parametrize('B', [1, 3])
 @pytest.mark.parametrize('P,f', [(8, 1), (8, 2), (8, 4), (7, 1), (7, 2), (5, 4)])
 def test_px_frames_equal_video_frames_uint8_on_materialised_float_panels(P, f, B):
-    from stylegan_directions_face_reenactment_amd.reenact import video_frames_px, video_frames_uint8
+    """The px launch on every panel layout against the frames of pool_images -> grid_frames_uint8 on materialised float panels
+    (util.composed).  The name is from when video_frames_uint8 supplied the expected bytes; that entry now runs the px kernels too, so
+    it would be no witness, and composed gives the bytes it gave."""
+    from stylegan_directions_face_reenactment_amd.reenact import video_frames_px
     key = 'cross.px.%d.%d.%d' % (P, f, B)
     x = floats((B, 3, P * f, P * f), key)
     per_row = [floats((B, 3, P, P), key + '.p%d' % k) for k in range(3)]
@@ -59,7 +63,7 @@ def test_px_frames_equal_video_frames_uint8_on_materialised_float_panels(P, f, B
     clamped = [min(max(i, 0), 3) for i in wild]
     checked = 0
     for swap_rb in (False, True):
-        ref = lambda panels, out=None: video_frames_uint8(x, panels, P, swap_rb=swap_rb, out=out)
+        ref = lambda panels, out=None: composed(x, panels, P, swap_rb, out)
         px = lambda panels, **kw: video_frames_px(x, panels, P, swap_rb=swap_rb, **kw)
         cases = [
             ('no left panel', px([]), ref([])),
@@ -94,18 +98,17 @@ def test_px_frames_equal_video_frames_uint8_on_materialised_float_panels(P, f, B
         checked += 3
     a, b = video_frames_px(x, [one, u8_rows], P, swap_rb=False), video_frames_px(x, [one, u8_rows], P, swap_rb=True)
     assert torch.equal(a.flip(3), b) and not torch.equal(a, b)
-    print('P=%d f=%d B=%d: %d layouts equal video_frames_uint8 byte for byte' % (P, f, B, checked))
+    print('P=%d f=%d B=%d: %d layouts equal pool -> grid byte for byte' % (P, f, B, checked))
 
 
 def want_left(x, panels, P, swap_rb):
-    from stylegan_directions_face_reenactment_amd.reenact import video_frames_uint8
-    return video_frames_uint8(x, panels, P, swap_rb=swap_rb)[:, :, :len(panels) * P]
+    return composed(x, panels, P, swap_rb, None)[:, :, :len(panels) * P]
 
 
 @pytest.mark.parametrize('P,f', [(8, 1), (8, 4)])
 def test_px_frames_from_unaligned_views(P, f):
     """x one float off 16 bytes takes the dword path; a uint8 table that starts at an odd byte takes byte loads: the same bytes."""
-    from stylegan_directions_face_reenactment_amd.reenact import video_frames_px, video_frames_uint8
+    from stylegan_directions_face_reenactment_amd.reenact import video_frames_px
     x = floats((3, 3, P * f, P * f), 'cross.off.%d' % f)
     one, u8 = floats((1, 3, P, P), 'cross.off.l'), crop_bytes((3, P, P, 3), 'cross.off.u')
     shifted = torch.empty(x.numel() + 1, device='cuda')[1:].view(x.shape).copy_(x)
@@ -113,7 +116,7 @@ def test_px_frames_from_unaligned_views(P, f):
     assert x.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 != 0 and shifted.is_contiguous()
     assert u8.data_ptr() % 4 == 0 and odd.data_ptr() % 2 == 1 and odd.is_contiguous()
     for swap_rb in (False, True):
-        want = video_frames_uint8(x, [one, as_float_panel(u8)], P, swap_rb=swap_rb)
+        want = composed(x, [one, as_float_panel(u8)], P, swap_rb, None)
         for xx in (x, shifted):
             for uu in (u8, odd):
                 assert torch.equal(video_frames_px(xx, [one, uu], P, swap_rb=swap_rb), want), (swap_rb, xx is x, uu is u8)
@@ -124,12 +127,12 @@ def test_px_frames_from_unaligned_views(P, f):
 
 def test_px_frames_uint8_map_over_all_256_values():
     """A [1,16,16,3] panel holding every byte value in every channel, against the float path and against the restated table."""
-    from stylegan_directions_face_reenactment_amd.reenact import uint8_panel_map, video_frames_px, video_frames_uint8
+    from stylegan_directions_face_reenactment_amd.reenact import uint8_panel_map, video_frames_px
     u8 = (torch.arange(16 * 16 * 3) * 7 % 256).to(torch.uint8).view(1, 16, 16, 3).cuda()
     assert sorted(set(u8.flatten().tolist())) == list(range(256))
     x = floats((1, 3, 16, 16), 'cross.map.x')
     got = video_frames_px(x, [u8], 16)
-    want = video_frames_uint8(x, [as_float_panel(u8)], 16)
+    want = composed(x, [as_float_panel(u8)], 16, False, None)
     table = uint8_panel_map().cuda()
     differ = int((got[:, :, :16] != u8).sum())
     print('exhaustive uint8 map: %d of 768 bytes differ from the input byte (the map is not the identity)' % differ)

@@ -10,7 +10,7 @@ public calls with the same chunks: the same kernels on the same numbers, equal b
 import pytest
 import torch
 
-from util import S, SEED, golden, hip_generator, maxabs
+from util import S, SEED, composed, golden, hip_generator, maxabs
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +25,6 @@ def frames_input(shape, key):
     flat[0], flat[1], flat[2], flat[3], flat[4] = 1.0, -1.0, -0.0, 1.25, -1.5          # exactly +-1, -0.0, beyond +-1
     assert float(x.abs().max()) > 1.0
     return x.cuda()
-
-
-def composed(x, panels, P, swap_rb, out):
-    """What exists: sgdfr_sweep_frames_f32 (pooled) -> sgdfr_grid_to_u8_f32."""
-    from stylegan_directions_face_reenactment_amd.reenact import grid_frames_uint8, pool_images
-    return grid_frames_uint8(list(panels) + [pool_images(x, P)], swap_rb=swap_rb, out=out)
 
 
 @pytest.mark.parametrize('B', [1, 3])
@@ -75,6 +69,34 @@ def test_fused_video_frames_from_a_view_off_16_bytes(P, f):
         want = composed(x, left, P, swap_rb, None)
         assert torch.equal(video_frames_uint8(x, left, P, swap_rb=swap_rb), want)
         assert torch.equal(video_frames_uint8(shifted, left, P, swap_rb=swap_rb), want)
+
+
+def test_video_frames_f32_entry_takes_stride_0_as_one_row_and_a_full_stride_as_one_per_row():
+    """sgdfr_video_frames_f32 below the Python entry, which never sends stride 0 at B = 1: the C entry describes its float panels to
+    the px kernels as tables of 1 row (stride 0) or B rows (stride 3 * P * P), whatever B is.  P = 7, f = 2: P * f = 14 takes the
+    dword path and a panel starts 3 * P = 21 bytes into a line.  Equal bytes with pool_images -> grid_frames_uint8; the NULL panel's
+    columns keep what `out` held."""
+    import ctypes
+    from stylegan_directions_face_reenactment_amd import _native as N
+    P, f = 7, 2
+    one, per_row = frames_input((1, 3, P, P), 'reen.vf.c.one'), frames_input((3, 3, P, P), 'reen.vf.c.rows')
+
+    def entry(x, panels, strides, swap_rb, out):
+        n = len(panels)
+        ptrs = (ctypes.c_void_p * n)(*[None if p is None else p.data_ptr() for p in panels])
+        N.call('sgdfr_video_frames_f32', N.ptr(x), x.shape[0], P, f, ptrs, (ctypes.c_int64 * n)(*strides), n, N.ptr(out), swap_rb, N.stream())
+        return out
+
+    fill = lambda B, K: torch.arange(B * P * K * P * 3, device='cuda').mul_(37).remainder_(251).to(torch.uint8).view(B, P, K * P, 3)
+    x1, x3 = frames_input((1, 3, P * f, P * f), 'reen.vf.c.x1'), frames_input((3, 3, P * f, P * f), 'reen.vf.c.x3')
+    for swap_rb in (0, 1):
+        want = composed(x1, [one], P, swap_rb, None)
+        for stride in (0, 3 * P * P):                                                   # B = 1: either stride is the panel's only row
+            assert torch.equal(entry(x1, [one], [stride], swap_rb, fill(1, 2)), want), (stride, swap_rb)
+        got = entry(x3, [one, per_row, None], [0, 3 * P * P, 0], swap_rb, fill(3, 4))
+        assert torch.equal(got, composed(x3, [one, per_row, None], P, swap_rb, fill(3, 4)))
+        assert torch.equal(got[:, :, 2 * P:3 * P], fill(3, 4)[:, :, 2 * P:3 * P])
+        assert not torch.equal(got[0, :, P:2 * P], got[1, :, P:2 * P]) and torch.equal(got[0, :, :P], got[2, :, :P])
 
 
 def test_fused_video_frames_python_entry_refuses_bad_shapes():

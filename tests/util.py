@@ -46,6 +46,13 @@ def hip_generator(size, cm, seed=SEED):
     return G.eval().cuda()
 
 
+def composed(x, panels, P, swap_rb, out):
+    """The frames of the video entries from the two launches that do not share their kernel: sgdfr_sweep_frames_f32 (pooled, anchored
+    on the float64 restatement of tests/test_gpu_sweeps.py) -> sgdfr_grid_to_u8_f32 (the host assembly of tests/dense_refs.py)."""
+    from stylegan_directions_face_reenactment_amd.reenact import grid_frames_uint8, pool_images
+    return grid_frames_uint8(list(panels) + [pool_images(x, P)], swap_rb=swap_rb, out=out)
+
+
 def image_digest(img, stride=4):
     d = img.detach().double().cpu()
     return {'sub': img.detach().cpu()[:, :, ::stride, ::stride].numpy(), 'rowsum': d.sum(3).numpy(),
