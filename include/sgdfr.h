@@ -869,6 +869,40 @@ int sgdfr_fan_forward_f32(const float* x, const float* faces, int rows, int H, i
                           float* heatmaps, float* pts, float* pts_img, float* boxes, float* debug, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* The rest of LandmarksEstimation (landmarks_estimation.py:155-181): flip_input, the Gaussian draw of fan_model/utils.py:13-60 and
+ * the 3D landmark type on ResNetDepth (fan_model/models.py:58-95 and :205-265, csrc/fandepth.hip).  Forward only.
+ * sgdfr_fan_flip_add_f32: hm2 [2 rows,68,64,64], rows 0..rows-1 the heatmaps of the crops and rows..2 rows-1 those of their mirrors
+ *   -> out[b,c,y,x] = hm2[b,c,y,x] + hm2[rows+b, pairs[c], y, 63-x], pairs = shuffle_lr's table (utils.py:256-260).
+ * sgdfr_fan_draw_f32: pts [rows,68,2] crop pixels (any float) -> maps [rows,68,256,256]: zeros and, where pts.x > 0 and the window
+ *   is not rejected by draw_gaussian's test, its 13x13 Gaussian (sigma 2) placed by the reference's 1-based index arithmetic.  The
+ *   table is _gaussian(13) evaluated in double on the host and rounded to float once.  A non-finite coordinate draws nothing.
+ * sgdfr_fandepth_prepack_f32: params = host array of 312 device pointers, every BatchNorm folded on the host: stem w0 [64,71,7,7],
+ *   b0 [64]; per bottleneck (50 = 3 + 8 + 36 + 3) w1 [P,Cin], b1 [P], w2 [P,P,3,3], b2 [P], w3 [4P,P], b3 [4P] and, for the first of
+ *   each layer only, the projection's wd [4P,Cin], bd [4P]; fc w [68,2048], b [68] -> pack of sgdfr_fandepth_pack_elems() floats.
+ * sgdfr_fandepth_network_f32: crop [rows,3,256,256] in [0,1] and maps [rows,68,256,256] (the 71 input channels, never concatenated)
+ *   -> depth [rows,68].  debug (NULL: off) receives sgdfr_fandepth_debug_elems(rows) floats: the stem [rows,64,128,128], the
+ *   max-pool [rows,64,64,64], the outputs of layer1..4 ([rows,256,64,64], [rows,512,32,32], [rows,1024,16,16], [rows,2048,8,8]) and
+ *   the pooled features [rows,2048] (AvgPool2d(7) on 8x8: rows and columns 0..6).
+ * sgdfr_fan_forward3d_f32: front, network (once on 2 rows crops with the mirrors behind when flip != 0, then flip_add), decode and,
+ *   when depth_pack is not NULL, draw, depth network and pts_img3 [rows,68,3] = (pts_img.x, pts_img.y, depth * (1 / (256 / (200
+ *   scale)))), each operation rounded on its own.  hm2 [2 rows,68,64,64] is scratch for flip != 0 (else NULL); maps
+ *   [rows,68,256,256], depth [rows,68] and pts_img3 are outputs of the 3D part (NULL without depth_pack).  workspace holds
+ *   sgdfr_fan_workspace_bytes(flip ? 2 rows : rows, H, W) bytes and debug sgdfr_fan_debug_elems of the same row count;
+ *   depth_workspace holds sgdfr_fandepth_workspace_bytes(rows) bytes.
+ * Deterministic (no float atomics), no host synchronisation, everything on `stream`. */
+int64_t sgdfr_fandepth_pack_elems(void);
+int64_t sgdfr_fandepth_debug_elems(int rows);
+int64_t sgdfr_fandepth_workspace_bytes(int rows);
+int sgdfr_fandepth_prepack_f32(const float* const* params, float* pack, void* stream);
+int sgdfr_fandepth_network_f32(const float* crop, const float* maps, int rows, const float* pack, float* depth, float* debug,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_fan_flip_add_f32(const float* hm2, int rows, float* out, void* stream);
+int sgdfr_fan_draw_f32(const float* pts, int rows, float* maps, void* stream);
+int sgdfr_fan_forward3d_f32(const float* x, const float* faces, int rows, int H, int W, int input_range, int flip, const float* pack,
+                            const float* depth_pack, float* hm2, float* heatmaps, float* pts, float* pts_img, float* boxes, float* maps,
+                            float* depth, float* pts_img3, float* debug, void* workspace, int64_t workspace_bytes,
+                            void* depth_workspace, int64_t depth_workspace_bytes, void* stream);
+
 /* The S3FD face detector in eval mode (libs/face_models/sfd/net_s3fd.py s3fd, detect.py:36-81 batch_detect, bbox.py:44-66 nms and
  * :93-111 decode, sfd_detector.py:31-47 detect_from_batch), csrc/s3fd.hip.  Forward only.
  * Images x [rows,3,H,W] fp32 with 0..255 values, 1..256 rows, each side 32..4096, rows*H*W <= 2^24.  subtract_mean != 0 subtracts

@@ -196,6 +196,13 @@ SIGNATURES['sgdfr_fan_forward_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _i, _c_f32p
                                        ctypes.c_void_p, _i64, ctypes.c_void_p]
 FAN_PARAMS = 735        # pointers sgdfr_fan_prepack_f32 takes
 FAN_RANGE_255, FAN_RANGE_GAN = 0, 1      # include/sgdfr.h SGDFR_FAN_RANGE_*
+SIGNATURES['sgdfr_fan_flip_add_f32'] = [_c_f32p, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_fan_draw_f32'] = [_c_f32p, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_fan_forward3d_f32'] = ([_c_f32p, _c_f32p, _i, _i, _i, _i, _i] + [_c_f32p] * 11 + [ctypes.c_void_p, _i64, ctypes.c_void_p,
+                                                                                                     _i64, ctypes.c_void_p])
+SIGNATURES['sgdfr_fandepth_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_fandepth_network_f32'] = [_c_f32p, _c_f32p, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+FANDEPTH_PARAMS = 312   # pointers sgdfr_fandepth_prepack_f32 takes
 _ip = ctypes.c_void_p                    # int* on the device
 SIGNATURES['sgdfr_s3fd_level_dims'] = [_i, _i, ctypes.POINTER(ctypes.c_int)]
 SIGNATURES['sgdfr_s3fd_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _c_f32p, ctypes.c_void_p]
@@ -260,6 +267,7 @@ SIZE_QUERIES = {
     'sgdfr_flame_pack_elems': 0, 'sgdfr_flame_saved_elems': 1, 'sgdfr_flame_workspace_bytes': 1,
     'sgdfr_deca_pack_elems': 0, 'sgdfr_deca_saved_elems': 1, 'sgdfr_deca_debug_elems': 1, 'sgdfr_deca_workspace_bytes': 3,
     'sgdfr_fan_pack_elems': 0, 'sgdfr_fan_debug_elems': 1, 'sgdfr_fan_workspace_bytes': 3,
+    'sgdfr_fandepth_pack_elems': 0, 'sgdfr_fandepth_debug_elems': 1, 'sgdfr_fandepth_workspace_bytes': 1,
     'sgdfr_s3fd_pack_elems': 0, 'sgdfr_s3fd_debug_elems': 3, 'sgdfr_s3fd_map_elems': 3, 'sgdfr_s3fd_workspace_bytes': 3,
     'sgdfr_e4e_pack_elems': 1, 'sgdfr_e4e_debug_elems': 2, 'sgdfr_e4e_workspace_bytes': 2,
     'sgdfr_facecrop_workspace_bytes': 4,

@@ -328,6 +328,96 @@ __global__ __launch_bounds__(64) void fan_boxes_kernel(const float* __restrict__
     if (t == 0) boxes[4 * b] = x0, boxes[4 * b + 1] = y0, boxes[4 * b + 2] = x1, boxes[4 * b + 3] = y1;
 }
 
+// ------------------------------------------------------------------ flip_input (landmarks_estimation.py:157-159)
+// rows B..2B-1 of the crop buffer = rows 0..B-1 mirrored along x: flip(inp), a copy
+__global__ __launch_bounds__(kThreads) void fan_mirror_kernel(float* __restrict__ crop, int B) {
+    const int64_t n = (int64_t)B * 3 * kInPlane;
+    for (int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * kThreads) {
+        const int u = (int)(idx % kIn);
+        crop[n + idx] = crop[idx - u + (kIn - 1 - u)];
+    }
+}
+
+// shuffle_lr's table (fan_model/utils.py:256-260)
+struct Pairs {
+    unsigned char at[kPts];
+};
+static Pairs flip_pairs() {
+    static const unsigned char t[kPts] = {16, 15, 14, 13, 12, 11, 10, 9,  8,  7,  6,  5,  4,  3,  2,  1,  0,  26, 25, 24, 23, 22, 21,
+                                          20, 19, 18, 17, 27, 28, 29, 30, 35, 34, 33, 32, 31, 45, 44, 43, 42, 47, 46, 39, 38, 37, 36,
+                                          41, 40, 54, 53, 52, 51, 50, 49, 48, 59, 58, 57, 56, 55, 64, 63, 62, 61, 60, 67, 66, 65};
+    Pairs p;
+    memcpy(p.at, t, sizeof(t));
+    return p;
+}
+
+// out[b,c,y,x] = hm2[b,c,y,x] + hm2[B+b, pairs[c], y, 63-x]: net(inp) + flip(net(flip(inp)), is_label=True)
+__global__ __launch_bounds__(kThreads) void fan_flip_add_kernel(const float* __restrict__ hm2, int B, Pairs pairs, float* __restrict__ out) {
+    const int64_t n = (int64_t)B * kPts * kMapPlane;
+    for (int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * kThreads) {
+        const int x = (int)(idx % kMap), y = (int)((idx / kMap) % kMap);
+        const int bc = (int)(idx / kMapPlane), b = bc / kPts, c = bc - b * kPts;
+        const int64_t other = ((int64_t)(B + b) * kPts + pairs.at[c]) * kMapPlane + y * kMap + (kMap - 1 - x);
+        out[idx] = hm2[idx] + hm2[other];
+    }
+}
+
+// ------------------------------------------------------------------ draw_gaussian (fan_model/utils.py:13-60, sigma = 2)
+constexpr int kGauss = 13;
+struct GaussTable {
+    float g[kGauss * kGauss];
+};
+// _gaussian(13): sigma 0.25 of the width, centre 7, evaluated in double and rounded to float once, as the store into the
+// reference's float32 array does
+static const GaussTable& gauss_table() {
+    static const GaussTable t = [] {
+        GaussTable r;
+        for (int i = 0; i < kGauss; ++i)
+            for (int j = 0; j < kGauss; ++j)
+                r.g[i * kGauss + j] = (float)(1 * exp(-(pow((j + 1 - 7.0) / (0.25 * kGauss), 2) / 2.0 + pow((i + 1 - 7.0) / (0.25 * kGauss), 2) / 2.0)));
+        return r;
+    }();
+    return t;
+}
+
+// the reference's 1-based ranges along one axis for ul = floor(p - 6), br = floor(p + 6) on a 256 map: image pixels i0 .. i1 take
+// table entries from g0 on (all 1-based, i1 < i0: nothing)
+__device__ __forceinline__ bool draw_range(float p, int& i0, int& i1, int& g0) {
+    const float lo = floorf(__fsub_rn(p, 6.0f)), hi = floorf(__fadd_rn(p, 6.0f));
+    if (!(lo > -1e6f && hi < 1e6f)) return false;      // also NaN; such a window is rejected below anyway
+    const int ul = (int)lo, br = (int)hi;
+    if (ul > kIn || br < 1) return false;
+    g0 = max(1, -ul), i0 = max(1, ul), i1 = min(br, kIn);
+    return true;
+}
+
+// one block per map: zeros, then the Gaussian.  Only one Gaussian lands in a map, so the clamp at 1 is a min.
+__global__ __launch_bounds__(kThreads) void fan_draw_kernel(const float* __restrict__ pts, GaussTable tab, float* __restrict__ maps) {
+    const int map = blockIdx.x, t = threadIdx.x;
+    float* m = maps + (int64_t)map * kInPlane;
+    for (int i = t; i < kInPlane; i += kThreads) m[i] = 0.f;
+    const float px = pts[2 * map], py = pts[2 * map + 1];
+    int x0, x1, gx, y0, y1, gy;
+    if (!(px > 0.f) || !draw_range(px, x0, x1, gx) || !draw_range(py, y0, y1, gy)) return;
+    __syncthreads();
+    if (t < kGauss * kGauss) {
+        const int dy = t / kGauss, dx = t - dy * kGauss;
+        const int iy = y0 + dy, ix = x0 + dx, jy = gy + dy, jx = gx + dx;      // 1-based
+        if (iy <= y1 && ix <= x1 && jy <= kGauss && jx <= kGauss) m[(iy - 1) * kIn + (ix - 1)] = fminf(tab.g[(jy - 1) * kGauss + (jx - 1)], 1.f);
+    }
+}
+
+// ------------------------------------------------------------------ pts_img3 (landmarks_estimation.py:179-181)
+// (pts_img.x, pts_img.y, depth * (1.0 / (256.0 / (200.0 * scale)))) in float32, every operation rounded on its own
+__global__ __launch_bounds__(kThreads) void fan_assemble_kernel(const float* __restrict__ pts_img, const float* __restrict__ depth,
+                                                                const float* __restrict__ faces, int B, float* __restrict__ out) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= B * kPts) return;
+    const float scale = face_of(faces + 4 * (i / kPts)).scale;
+    const float k = __fdiv_rn(1.0f, __fdiv_rn(256.0f, __fmul_rn(200.0f, scale)));
+    out[3 * i] = pts_img[2 * i], out[3 * i + 1] = pts_img[2 * i + 1], out[3 * i + 2] = __fmul_rn(depth[i], k);
+}
+
 // ------------------------------------------------------------------ host side
 static int launch_conv(const ConvArgs& a0, int ks, bool ext, float* part, hipStream_t st) {
     ConvArgs a = a0;
@@ -655,4 +745,59 @@ extern "C" int sgdfr_fan_forward_f32(const float* x, const float* faces, int row
     if (check_launch("fan front")) return 2;
     if (run_network(crop, rows, pack, heatmaps, debug, wsf, st)) return 2;
     return run_decode(heatmaps, faces, rows, pts, pts_img, boxes, st);
+}
+
+extern "C" int sgdfr_fan_flip_add_f32(const float* hm2, int rows, float* out, void* stream) {
+    SGDFR_REQUIRE(rows >= 1 && 2 * rows <= kMaxRows, "fan_flip_add: unsupported size (%d rows)", rows);
+    SGDFR_REQUIRE(hm2 && out, "fan_flip_add: null pointer");
+    hipLaunchKernelGGL(fan_flip_add_kernel, dim3(grid_1d((int64_t)rows * kPts * kMapPlane)), dim3(kThreads), 0, as_stream(stream), hm2, rows,
+                       flip_pairs(), out);
+    return check_launch("fan flip add");
+}
+
+extern "C" int sgdfr_fan_draw_f32(const float* pts, int rows, float* maps, void* stream) {
+    SGDFR_REQUIRE(rows_ok(rows), "fan_draw: unsupported size (%d rows)", rows);
+    SGDFR_REQUIRE(pts && maps, "fan_draw: null pointer");
+    hipLaunchKernelGGL(fan_draw_kernel, dim3(rows * kPts), dim3(kThreads), 0, as_stream(stream), pts, gauss_table(), maps);
+    return check_launch("fan draw");
+}
+
+extern "C" int sgdfr_fan_forward3d_f32(const float* x, const float* faces, int rows, int H, int W, int input_range, int flip,
+                                       const float* pack, const float* depth_pack, float* hm2, float* heatmaps, float* pts, float* pts_img,
+                                       float* boxes, float* maps, float* depth, float* pts_img3, float* debug, void* workspace,
+                                       int64_t workspace_bytes, void* depth_workspace, int64_t depth_workspace_bytes, void* stream) {
+    const int net_rows = flip ? 2 * rows : rows;      // the mirrors ride behind the crops: a flip call takes half the rows
+    SGDFR_REQUIRE(rows >= 1 && size_ok(net_rows, H, W), "fan_forward3d: unsupported size (%d rows of %dx%d, flip %d)", rows, H, W, flip);
+    SGDFR_REQUIRE(input_range == SGDFR_FAN_RANGE_255 || input_range == SGDFR_FAN_RANGE_GAN, "fan_forward3d: unknown input_range %d",
+                  input_range);
+    SGDFR_REQUIRE(x && faces && pack && heatmaps && pts && pts_img && workspace && (!flip || hm2), "fan_forward3d: null pointer");
+    SGDFR_REQUIRE(!depth_pack || (maps && depth && pts_img3 && depth_workspace), "fan_forward3d: null pointer (3D outputs)");
+    const WsLayout wl = ws_layout(net_rows);
+    SGDFR_REQUIRE(wl.total * (int64_t)sizeof(float) <= workspace_bytes, "fan_forward3d: workspace of %lld bytes, %d rows need %lld",
+                  (long long)workspace_bytes, net_rows, (long long)(wl.total * (int64_t)sizeof(float)));
+    float* wsf = reinterpret_cast<float*>(workspace);
+    hipStream_t st = as_stream(stream);
+    float* crop = wsf + wl.crop;
+    hipLaunchKernelGGL(fan_front_kernel, dim3(grid_1d((int64_t)rows * 3 * kInPlane)), dim3(kThreads), 0, st, x, faces, rows, H, W,
+                       input_range == SGDFR_FAN_RANGE_GAN ? 1 : 0, crop);
+    if (check_launch("fan front")) return 2;
+    if (flip) {
+        hipLaunchKernelGGL(fan_mirror_kernel, dim3(grid_1d((int64_t)rows * 3 * kInPlane)), dim3(kThreads), 0, st, crop, rows);
+        if (check_launch("fan mirror")) return 2;
+        if (run_network(crop, net_rows, pack, hm2, debug, wsf, st)) return 2;
+        hipLaunchKernelGGL(fan_flip_add_kernel, dim3(grid_1d((int64_t)rows * kPts * kMapPlane)), dim3(kThreads), 0, st, hm2, rows, flip_pairs(),
+                           heatmaps);
+        if (check_launch("fan flip add")) return 2;
+    } else if (run_network(crop, rows, pack, heatmaps, debug, wsf, st)) {
+        return 2;
+    }
+    if (run_decode(heatmaps, faces, rows, pts, pts_img, boxes, st)) return 2;
+    if (!depth_pack) return 0;
+    hipLaunchKernelGGL(fan_draw_kernel, dim3(rows * kPts), dim3(kThreads), 0, st, pts, gauss_table(), maps);
+    if (check_launch("fan draw")) return 2;
+    // the crop rows 0..rows-1 are read by the stem only and are still the front's
+    if (sgdfr_fandepth_network_f32(crop, maps, rows, depth_pack, depth, nullptr, depth_workspace, depth_workspace_bytes, stream)) return 2;
+    hipLaunchKernelGGL(fan_assemble_kernel, dim3((rows * kPts + kThreads - 1) / kThreads), dim3(kThreads), 0, st, pts_img, depth, faces, rows,
+                       pts_img3);
+    return check_launch("fan assemble");
 }

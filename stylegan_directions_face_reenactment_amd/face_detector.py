@@ -301,17 +301,21 @@ def select_face(boxes, kept, rule='first'):
     return faces * has.view(-1, 1).to(faces.dtype), has
 
 
-def detect_landmarks(det, fan, images, rule='first', input_range='255', capacity=CAPACITY):
+def detect_landmarks(det, fan, images, rule='first', input_range='255', capacity=CAPACITY, flip_input=False, depth_net=None):
     """Image -> face box -> 68 landmarks -> 'kpt68' box on one stream with no host round trip: detect, select_face,
     landmarks.get_landmarks, landmarks.kpt68_boxes.  images [B,3,H,W] float32: 0..255 values (input_range='255') or GAN-range [-1,1]
     (input_range='gan': mapped to 0..255 in front of the detector, as in front of the landmark network).
     Returns (pts_img [B,68,2], boxes [B,4] for deca.crop_matrix, has_face [B] bool); rows with has_face False found no face under
-    `rule` and their landmarks and boxes mean nothing."""
+    `rule` and their landmarks and boxes mean nothing.  flip_input adds the mirrored pass of the landmark network; with `depth_net`
+    (landmarks.ResNetDepth) the landmarks are the 3D type's, pts_img [B,68,3], and the box comes from its first two columns."""
     if input_range not in L.RANGES:
         raise ValueError("face_detector: input_range must be '255' or 'gan', got %r" % (input_range,))
     _check_images(images)
     x255 = images if input_range == '255' else (images.clamp(-1, 1) + 1) / (2 + 1e-5) * 255.0
     boxes, kept, _ = detect(det, x255, capacity)
     faces, has = select_face(boxes, kept, rule)
-    pts_img, _, _ = L.get_landmarks(fan, images, faces, input_range=input_range)
+    if depth_net is not None:
+        pts_img, _, _ = L.get_landmarks_3d(fan, depth_net, images, faces, input_range=input_range, flip_input=flip_input)
+        return pts_img, L.kpt68_boxes(pts_img[..., :2]), has
+    pts_img, _, _ = L.get_landmarks(fan, images, faces, input_range=input_range, flip_input=flip_input)
     return pts_img, L.kpt68_boxes(pts_img), has

@@ -20,7 +20,18 @@ torchvision the reference was written for.  torchvision was not available when t
 against F.interpolate composed that way: the composition itself is UNVERIFIED against torchvision.
 
 Face boxes come in as numbers or as a device tensor; face_detector.py (S3FD on csrc/s3fd.hip) produces them and
-face_detector.detect_landmarks chains the two.  The 3D landmark type (ResNetDepth) and flip_input are not built.
+face_detector.detect_landmarks chains the two.
+
+The rest of the class (landmarks_estimation.py:155-181): `get_landmarks(..., flip_input=True)` runs the network once on the crops
+with their mirrors behind them and decodes the sum net(inp) + flip(net(flip(inp)), is_label=True); `get_landmarks_3d` is the 3D
+landmark type, the class's default: a 13x13 Gaussian is drawn per landmark (fan_model/utils.py:13-60), `ResNetDepth`
+(fan_model/models.py:205-265, csrc/fandepth.hip: 155 convs with every BatchNorm folded into its filters, ~234 MB pack) reads the
+crop and the 68 maps through a stem that gathers from both tensors, and pts_img becomes [B,68,3].
+
+    depth_net = ResNetDepth(); depth_net.load_state_dict(sd); depth_net = depth_net.cuda().eval()     # 'module.' prefix stripped
+    pts_img3, pts, heatmaps = get_landmarks_3d(fan, depth_net, images, faces, flip_input=False)
+
+`flip_add`, `draw` and `depth_network` are the pieces alone.
 """
 import torch
 from torch import nn
@@ -142,6 +153,73 @@ class FAN(PackedWeights, nn.Module):
         return network(self, crop)
 
 
+class _Bottleneck(nn.Module):
+    """models.py Bottleneck(inplanes, planes, stride, downsample): conv1x1 -> conv3x3 at the stride -> conv1x1, each with its BatchNorm,
+    plus the (projected) input.  Weights only."""
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.downsample = downsample
+
+
+class ResNetDepth(PackedWeights, nn.Module):
+    """models.ResNetDepth(Bottleneck, [3, 8, 36, 3], 68): weights only, the reference's 932 state-dict keys (its `depth` checkpoint
+    loads once the 'module.' prefix is stripped, as landmarks_estimation.py:136-138 does).  forward(crop [B,3,256,256] in [0,1], maps
+    [B,68,256,256]) -> depth [B,68]."""
+    PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_fandepth_prepack_f32', 'sgdfr_fandepth_pack_elems', N.FANDEPTH_PARAMS
+    TRAIN_ERROR = 'ResNetDepth: the HIP kernels run the network in eval mode only (running BatchNorm statistics); call .eval()'
+    GRAD_ERROR = ('ResNetDepth: the HIP kernels are forward only and give no gradient for the weights; keep every parameter at '
+                  'requires_grad=False')
+    LAYERS = (3, 8, 36, 3)
+
+    def __init__(self):
+        super().__init__()
+        self.inplanes = 64
+        self.conv1 = nn.Conv2d(3 + POINTS, 64, 7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        for i, (planes, blocks) in enumerate(zip((64, 128, 256, 512), self.LAYERS)):
+            self.add_module('layer%d' % (i + 1), self._make_layer(planes, blocks, 1 if i == 0 else 2))
+        self.fc = nn.Linear(2048, POINTS)
+        for p in self.parameters():
+            p.requires_grad = False
+
+    def _make_layer(self, planes, blocks, stride):
+        downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * 4, 1, stride=stride, bias=False), nn.BatchNorm2d(planes * 4))
+        layers = [_Bottleneck(self.inplanes, planes, stride, downsample)]
+        self.inplanes = planes * 4
+        layers += [_Bottleneck(self.inplanes, planes) for _ in range(1, blocks)]
+        return nn.Sequential(*layers)
+
+    def bottlenecks(self):
+        """The 50 bottlenecks in forward order."""
+        return [b for i in range(4) for b in getattr(self, 'layer%d' % (i + 1))]
+
+    def folded(self, dtype=torch.float32):
+        """The 312 tensors sgdfr_fandepth_prepack_f32 takes, every BatchNorm folded into its conv in fp64 on the parameters' device,
+        returned in `dtype`: stem w, b; per bottleneck w1, b1, w2, b2, w3, b3 and, behind the first of a layer, wd, bd; fc w, b."""
+        def fold(conv, bn):
+            g = bn.weight.detach().double() * torch.rsqrt(bn.running_var.detach().double() + bn.eps)
+            return conv.weight.detach().double() * g.view(-1, 1, 1, 1), bn.bias.detach().double() - bn.running_mean.detach().double() * g
+
+        out = list(fold(self.conv1, self.bn1))
+        for b in self.bottlenecks():
+            for conv, bn in ((b.conv1, b.bn1), (b.conv2, b.bn2), (b.conv3, b.bn3)):
+                out += list(fold(conv, bn))
+            if b.downsample is not None:
+                out += list(fold(b.downsample[0], b.downsample[1]))
+        out += [self.fc.weight.detach().double(), self.fc.bias.detach().double()]
+        return [v.to(dtype).contiguous() for v in out]
+
+    def forward(self, crop, maps):
+        return depth_network(self, crop, maps)
+
+
 # ---------------------------------------------------------------------------------------------------------------- checks
 def _faces(faces, images):
     """[B,4] float32 x0, y0, x1, y1 on the images' device from a [B,4] / [B,5] tensor or numbers (a fifth column, the score, is
@@ -243,6 +321,69 @@ def decode(heatmaps, faces):
     return pts_img, pts, boxes
 
 
+def flip_add(hm2):
+    """The sum of flip_input (landmarks_estimation.py:157-159) alone: hm2 [2B,68,64,64], rows 0..B-1 the heatmaps of the crops and
+    rows B..2B-1 those of their mirrors -> [B,68,64,64] = hm2[:B] + flip(hm2[B:], is_label=True)."""
+    if (not torch.is_tensor(hm2) or hm2.dim() != 4 or tuple(hm2.shape[1:]) != (POINTS, MAP, MAP) or hm2.shape[0] < 2
+            or hm2.shape[0] % 2):
+        raise ValueError('landmarks: expected [2B,68,64,64] heatmaps, got %s' % (tuple(hm2.shape) if torch.is_tensor(hm2) else type(hm2),))
+    N.require_device(hm2)
+    h = N.f32c(hm2.detach())
+    B = h.shape[0] // 2
+    N.size('sgdfr_fan_debug_elems', 2 * B, error=_unsupported(B, MAP, MAP))
+    out = torch.empty((B, POINTS, MAP, MAP), dtype=torch.float32, device=h.device)
+    N.call('sgdfr_fan_flip_add_f32', N.ptr(h), B, N.ptr(out), N.stream())
+    return out
+
+
+def draw(pts):
+    """draw_gaussian (fan_model/utils.py:39-60, sigma 2) as get_landmarks calls it (:166-171): pts [B,68,2] crop pixels ->
+    [B,68,256,256] maps, zero but for one 13x13 Gaussian each, and zero throughout where pts.x <= 0 or the window misses the map."""
+    if not torch.is_tensor(pts) or pts.dim() != 3 or tuple(pts.shape[1:]) != (POINTS, 2) or pts.shape[0] < 1:
+        raise ValueError('landmarks: expected [B,68,2] points, got %s' % (tuple(pts.shape) if torch.is_tensor(pts) else type(pts),))
+    N.require_device(pts)
+    p = N.f32c(pts.detach())
+    B = p.shape[0]
+    N.size('sgdfr_fan_debug_elems', B, error=_unsupported(B, CROP, CROP))
+    maps = torch.empty((B, POINTS, CROP, CROP), dtype=torch.float32, device=p.device)
+    N.call('sgdfr_fan_draw_f32', N.ptr(p), B, N.ptr(maps), N.stream())
+    return maps
+
+
+def depth_debug_views(debug, rows):
+    """The debug buffer as named views (csrc/fandepth.hip's DebugLayout): stem, pool, layer (four), feat."""
+    out, take = {}, views(debug, rows)
+    out['stem'] = take((64, 128, 128))
+    out['pool'] = take((64, 64, 64))
+    out['layer'] = [take((256 << s, 64 >> s, 64 >> s)) for s in range(4)]
+    out['feat'] = take((2048,))
+    take.done()
+    return out
+
+
+def _depth_workspace(rows, device):
+    return N.workspace('sgdfr_fandepth_workspace_bytes', device, rows, error=_unsupported(rows, CROP, CROP))
+
+
+def depth_network(depth_net, crops, maps, debug=False):
+    """ResNetDepth alone: crops [B,3,256,256] in [0,1] and maps [B,68,256,256] (the reference concatenates them; the stem reads both)
+    -> depth [B,68]; with debug=True (depth, depth_debug_views dict)."""
+    depth_net.check()
+    _check_crop(crops)
+    if not torch.is_tensor(maps) or tuple(maps.shape) != (crops.shape[0], POINTS, CROP, CROP):
+        raise ValueError('landmarks: expected [%d,68,256,256] maps, got %s' % (crops.shape[0], tuple(maps.shape) if torch.is_tensor(maps)
+                                                                                 else type(maps),))
+    N.require_device(maps)
+    c, m = N.f32c(crops.detach()), N.f32c(maps.detach())
+    B = c.shape[0]
+    ws, nbytes = _depth_workspace(B, c.device)
+    depth = torch.empty((B, POINTS), dtype=torch.float32, device=c.device)
+    dbg = torch.empty(N.load().sgdfr_fandepth_debug_elems(B), dtype=torch.float32, device=c.device) if debug else None
+    N.call('sgdfr_fandepth_network_f32', N.ptr(c), N.ptr(m), B, N.ptr(depth_net.packed()), N.ptr(depth), N.ptr(dbg), N.ptr(ws), nbytes,
+           N.stream())
+    return (depth, depth_debug_views(dbg, B)) if debug else depth
+
+
 def _forward(fan, images, faces, input_range, debug):
     fan.check()
     x, f, code = _prepare(images, faces, input_range)
@@ -260,14 +401,53 @@ def _forward(fan, images, faces, input_range, debug):
     return pts_img, pts, hm, boxes, dbg
 
 
-def get_landmarks(fan, images, faces, input_range='255'):
-    """LandmarksEstimation.get_landmarks for a whole batch in one pass.  images [B,3,H,W] float32 on the device, 0..255 values
-    (input_range='255', as the reference takes them) or GAN-range [-1,1] (input_range='gan': torch_range_1_to_255 is applied, the map
-    deca.encode applies, so one generated tensor feeds both); faces [B,4] (or [B,5], the score ignored) x0, y0, x1, y1 from the
-    caller's detector, a tensor or numbers.  Returns (pts_img [B,68,2] image pixels, integer-valued float32; pts [B,68,2] crop
-    pixels = preds * 4; heatmaps [B,68,64,64] of the last stack).  No host synchronisation; nothing is differentiable."""
+def _forward3d(fan, depth_net, images, faces, input_range, flip_input):
+    """One sgdfr_fan_forward3d_f32 call: the network runs on 2B rows with flip_input (the mirrors behind the crops), so workspace and
+    row limit are those of 2B rows; depth_net None stops behind the decode."""
+    fan.check()
+    if depth_net is not None:
+        depth_net.check()
+    x, f, code = _prepare(images, faces, input_range)
+    B, _, H, W = x.shape
+    dev = x.device
+    rows = 2 * B if flip_input else B
+    ws, nbytes = N.workspace('sgdfr_fan_workspace_bytes', dev, rows, H, W, error=_unsupported(rows, H, W))
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    hm2 = new(rows, POINTS, MAP, MAP) if flip_input else None
+    hm, pts, pts_img, boxes = new(B, POINTS, MAP, MAP), new(B, POINTS, 2), new(B, POINTS, 2), new(B, 4)
+    maps = depth = pts_img3 = dws = dpack = None
+    dbytes = 0
+    if depth_net is not None:
+        dws, dbytes = _depth_workspace(B, dev)
+        maps, depth, pts_img3, dpack = new(B, POINTS, CROP, CROP), new(B, POINTS), new(B, POINTS, 3), depth_net.packed()
+    N.call('sgdfr_fan_forward3d_f32', N.ptr(x), N.ptr(f), B, H, W, code, 1 if flip_input else 0, N.ptr(fan.packed()), N.ptr(dpack),
+           N.ptr(hm2), N.ptr(hm), N.ptr(pts), N.ptr(pts_img), N.ptr(boxes), N.ptr(maps), N.ptr(depth), N.ptr(pts_img3), None, N.ptr(ws),
+           nbytes, N.ptr(dws), dbytes, N.stream())
+    return pts_img3, pts_img, pts, hm, depth, maps
+
+
+def get_landmarks(fan, images, faces, input_range='255', flip_input=False):
+    """LandmarksEstimation.get_landmarks (2D type) for a whole batch in one pass.  images [B,3,H,W] float32 on the device, 0..255
+    values (input_range='255', as the reference takes them) or GAN-range [-1,1] (input_range='gan': torch_range_1_to_255 is applied,
+    the map deca.encode applies, so one generated tensor feeds both); faces [B,4] (or [B,5], the score ignored) x0, y0, x1, y1 from the
+    caller's detector, a tensor or numbers.  flip_input=True adds the heatmaps of the mirrored crop (:157-159) in front of the decode:
+    the network then runs on 2B rows, and a call takes half as many images.  Returns (pts_img [B,68,2] image pixels, integer-valued
+    float32; pts [B,68,2] crop pixels = preds * 4; heatmaps [B,68,64,64] of the last stack, the sum with flip_input).  No host
+    synchronisation; nothing is differentiable."""
+    if flip_input:
+        _, pts_img, pts, hm, _, _ = _forward3d(fan, None, images, faces, input_range, True)
+        return pts_img, pts, hm
     pts_img, pts, hm, _, _ = _forward(fan, images, faces, input_range, False)
     return pts_img, pts, hm
+
+
+def get_landmarks_3d(fan, depth_net, images, faces, input_range='255', flip_input=False):
+    """LandmarksEstimation.get_landmarks with the 3D landmark type, the class's default (:165-181): behind the decode one Gaussian
+    per landmark is drawn at pts, ResNetDepth reads the crop with the 68 maps, and z = depth * (1 / (256 / (200 scale))) joins the
+    image coordinates.  Returns (pts_img [B,68,3], pts [B,68,2], heatmaps [B,68,64,64]); the first two columns of pts_img are
+    get_landmarks' own.  One native call, no host synchronisation."""
+    pts_img3, _, pts, hm, _, _ = _forward3d(fan, depth_net, images, faces, input_range, flip_input)
+    return pts_img3, pts, hm
 
 
 def run_debug(fan, images, faces, input_range='255'):

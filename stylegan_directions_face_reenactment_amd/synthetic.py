@@ -307,6 +307,43 @@ def synthetic_fan_state(seed):
     return out
 
 
+FAN_DEPTH_FC = (10.0, 30.0, 10.0)      # synthetic_fan_depth_state: fc filter gain on N(0, 1/fan_in), fc bias mean and spread
+
+
+def synthetic_fan_depth_state(seed):
+    """Seeded ResNetDepth state dict in the 932 keys of fan_model/models.py ResNetDepth (landmarks.ResNetDepth) that keeps
+    activations in range through the 50 bottlenecks: conv filters N(0, 2/fan_in), BatchNorm statistics near (0, 1) and scales near 1,
+    but the scale of every bottleneck's last BatchNorm (bn3) around 0.2, so that a block adds a few per cent to the variance its
+    shortcut carries instead of doubling it (plain He initialisation puts the depths at 2e8); the linear layer is scaled so that
+    the 68 depths come out of order 1 to 100.  234 MB: regenerated from the seed wherever it is needed, never stored."""
+    from collections import OrderedDict
+    from .landmarks import ResNetDepth
+    gain, bias_mean, bias_std = FAN_DEPTH_FC
+    out = OrderedDict()
+    for key, t in ResNetDepth().state_dict().items():
+        shape = tuple(t.shape)
+        if key.endswith('num_batches_tracked'):
+            out[key] = torch.zeros(shape, dtype=torch.int64)
+        elif key.endswith('running_var'):
+            v = counter_normal(seed, key, int(np.prod(shape))) * 0.2 + 1.0
+            out[key] = torch.from_numpy(np.maximum(v, 0.3).astype(np.float32).reshape(shape))
+        elif key.endswith('running_mean'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.1)
+        elif len(shape) == 4:
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))))
+        elif key == 'fc.weight':
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(gain * np.sqrt(1.0 / shape[1])))
+        elif key == 'fc.bias':
+            out[key] = counter_tensor(seed, key, shape, bias_mean, bias_std)
+        elif key.endswith('.bias'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.05)
+        elif key.endswith('.weight'):                             # BatchNorm scale
+            out[key] = counter_tensor(seed, key, shape, 0.2, 0.02) if key.endswith('.bn3.weight') else counter_tensor(seed, key, shape, 1.0, 0.1)
+        else:
+            raise KeyError(key)
+    return out
+
+
 # synthetic_s3fd_state: per level (conf filter gain, loc filter gain, face-logit bias); gains multiply N(0, 1/fan_in).  The figures
 # are tuned at seed 20261018 (scripts/make_golden_s3fd.py): behind the L2Norm most of a logit is a constant over the map (the taps
 # are positive), so the conf gains of levels 0-2 are large to give the part that varies a spread of 4-5, and the biases centre it.
