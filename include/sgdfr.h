@@ -260,7 +260,16 @@ int sgdfr_torgb_fwd_f32(const float* x, const float* w_rgb, const float* s, cons
  *                                      transpose_flip = 1 packs the adjoint conv (Cin outputs, Cout inputs, taps rotated),
  *                                      2 the adjoint of the transposed conv (channels swapped, taps stored phase by phase):
  *                                      dL/dx of the plain conv is then the same PLAIN3 kernel
- *   sgdfr_modconv2d_split_supported:   1 when the shape can use it (Cin % 16 == 0, Cout % 64 == 0, tileable H x W)
+ *   sgdfr_modconv2d_split_supported:   1 when the shape can use it.  Every mode: Cin % 16 == 0 and a tileable H x W.
+ *                                      PLAIN3, UP3: Cout % 64 == 0, or Cout % 64 == 32 (forward packs: the last cout tile is
+ *                                      half padding).  DOWN3: Cout % 128 == 0.  Tileable -- PLAIN3, W <= 64: 256 (Cout % 128
+ *                                      == 0) or 512 pixels are whole rows of whole images (PT % W == 0 and H W % PT == 0) or
+ *                                      whole images (PT % (H W) == 0); W > 64: W % 64 == 0 and H % (PT / 64) == 0.  UP3, DOWN3:
+ *                                      any H; the staged range of PT + W + 3 positions and the style table must fit the LDS,
+ *                                      which ends UP3 at W = 701 and DOWN3 at W = 381.  A pre-split input
+ *                                      (..._split_xin_supported) needs more: PLAIN3 every supported shape; UP3 Cout % 128 != 0
+ *                                      or the deep plan (B (H+1) (W+1) (Cout / 64) >= 65536), and room for a third weight slot
+ *                                      on the row-stage plan (W <= 637 at Cin = 16, 573 at Cin = 512); DOWN3 as above.  tests/test_cpu_split_edges.py pins each of these from both sides.
  *   sgdfr_modconv2d_split_f32:         arguments as sgdfr_modconv2d_wino_f32 with wsp in place of u, plus mode:
  *                                      PLAIN3, or UP3 = stride-2 transposed conv into parity planes
  *                                      [B,Cout,4,H+1,W+1] exactly as sgdfr_modconv2d_fwd_f32(mode UP3) writes them;
@@ -326,6 +335,10 @@ int sgdfr_modconv2d_split_cout_tiles(int B, int Cin, int Cout, int H, int W, int
 /* the cout tiling of a launch with x_is_split = 1 and ksplit <= 1 (its tiling plan may differ: T of rgb_part [B][T*3][H*W]) */
 int sgdfr_modconv2d_split_cout_tiles_xin(int B, int Cin, int Cout, int H, int W, int mode);
 int sgdfr_modconv2d_split_ksplit_hint(int B, int Cin, int Cout, int H, int W, int mode);
+/* Host-only, for tests: the tiling plan of a launch (xin_whole = 1: x_is_split = 1 and ksplit <= 1) as
+ * cfg | NEX << 4 | simgs << 8 | half cout tile << 20 (cfg: the plan index of csrc/split.hip, NEX: staging slots per thread,
+ * simgs: images a pixel tile may touch), or -1 when the shape is not supported. */
+int sgdfr_modconv2d_split_plan_info(int B, int Cin, int Cout, int H, int W, int mode, int xin_whole);
 
 /* ---- The plain 3x3 modulated conv in 1-D Winograd form on the split-operand matrix cores (csrc/wsplit.hip; replaces the same
  * reference lines as sgdfr_modconv2d_split_f32 mode PLAIN3: ModulatedConv2d.forward model.py:232-273 + NoiseInjection

@@ -405,6 +405,19 @@ extern "C" int sgdfr_modconv2d_split_cout_tiles_xin(int B, int Cin, int Cout, in
     return split_plan(B, Cin, Cout, H, W, mode, &p, true) ? p.n_cout_tiles : 0;
 }
 
+// Host-only: the plan a launch of this shape takes (xin_whole: pre-split input and no K slices), for tests that must tell the
+// instantiations apart: cfg | NEX << 4 | simgs << 8 | half cout tile << 20, or -1 when the shape is not supported.  NEX = the staging-slot
+// count launch_split picks for the plan's own block size (dense planes: plane_stride = 0).
+extern "C" int sgdfr_modconv2d_split_plan_info(int B, int Cin, int Cout, int H, int W, int mode, int xin_whole) {
+    SplitParams p;
+    const SplitPlan* plan = split_plan(B, Cin, Cout, H, W, mode, &p, xin_whole != 0);
+    if (!plan) return -1;
+    const int nthr = plan->nw * 64, nex = (2 * p.xs + nthr - 1) / nthr;
+    const int nex_max = mode == SGDFR_MODE_DOWN3 ? 3 : 4;
+    const int half = (plan->nt == 64 && Cout % 64 == 32) ? 1 : 0;
+    return plan->cfg | (nex <= 2 ? 2 : nex == 3 ? 3 : nex_max) << 4 | p.simgs << 8 | half << 20;
+}
+
 // cout tiles of 64, + a 16-byte trailer (SGDFR_SPLIT_FP16F8 packs keep max |w * scale| there: the source of their fp8 exponent)
 static int64_t split_pack_body_elems(int n_out, int n_in) { return (int64_t)((n_out + 63) / 64 * 64) * n_in * 9 * 2; }
 extern "C" int64_t sgdfr_modconv_prepack_split_elems(int Cout, int Cin) { return split_pack_body_elems(Cout, Cin) + 8; }
