@@ -1046,6 +1046,65 @@ int sgdfr_shaperender_forward_f32(const float* vertices, const float* projected,
                                   const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S, const float* lights,
                                   int light_rows, int L, const float* background, int gan_range, float* shape, float* alpha,
                                   int* pix_to_face, float* zbuf, float* bary, void* workspace, int64_t workspace_bytes, void* stream);
+/* sgdfr_shaperender_detail_f32: sgdfr_shaperender_forward_f32 with the detail panel of DECA.decode_deca (deca.py:187-189) from the same
+ *   rasterisation.  In addition: face_uv [F,3,2], the first two components of the renderer's face_uvcoords; uv_normals [rows,3,Su,Su], the
+ *   UV detail normal map; Su 1..4096.  vertices, the vertex table and lights are always needed.  Every output may be NULL:
+ *   shape, alpha, pix_to_face, zbuf, bary as above (shape has the bits sgdfr_shaperender_forward_f32 writes);
+ *   grid [rows,S,S,2] = g = sum_k w_k face_uv[f][k], (0, 0) where no face covers (ops['grid']);
+ *   detail_normal_images [rows,3,S,S] = N = covered * bilinear(uv_normals[row], g), with F.grid_sample's rules at align_corners False and
+ *     zero padding: ix = ((g.x + 1) Su - 1) / 2, iy likewise, the four neighbours weighted (1 - frac) and frac, a neighbour outside the
+ *     map adding nothing;
+ *   shape_detail [rows,3,S,S]: the expression of `shape` with the shading normal replaced by N (albedo, alpha, background, gan_range as
+ *     above).
+ *   The reference adds z_offset to the projected vertices in place on each of its three render calls; with an orthographic projection
+ *   that changes nothing while |z| < 10, and here z_offset is applied once. */
+int sgdfr_shaperender_detail_f32(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V,
+                                 const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S, const float* lights,
+                                 int light_rows, int L, const float* background, int gan_range, const float* face_uv,
+                                 const float* uv_normals, int Su, float* shape, float* shape_detail, float* grid,
+                                 float* detail_normal_images, float* alpha, int* pix_to_face, float* zbuf, float* bary, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
+
+/* DECA's detail path in eval mode (libs/DECA/decalib/models/decoders.py Generator(181, 1, 0.01, 'bilinear'), deca.py:114-141
+ * displacement2normal / displacement2vertex, utils/renderer.py:331-340 world2uv), csrc/detail.hip.  Forward only.
+ * D_detail: latent [rows,181] = cat(pose[:, 3:], exp, detail) -> Linear 181->8192 + BatchNorm(128), seen as [rows,128,8,8] -> five times
+ *   (2x bilinear upsample, conv3x3 pad 1, BatchNorm, LeakyReLU 0.2) to 128@16^2, 64@32^2, 64@64^2, 32@128^2, 16@256^2 -> conv3x3 16->1,
+ *   tanh, * out_scale -> uv_z [rows,1,256,256].  1..256 rows.  The upsample is upsample_bilinear2d at align_corners False: source
+ *   coordinate max(0, (i + 0.5) / 2 - 0.5), upper neighbour clamped to h - 1; the conv's zero padding applies to the upsampled map.
+ * sgdfr_detail_prepack_f32: params = host array of 14 device pointers, BatchNorms folded on the host (the five behind the convs are
+ *   nn.BatchNorm2d(C, 0.8): eps = 0.8): the Linear's weight [8192,181] and bias [8192] with the first BatchNorm folded in per channel
+ *   c = row / 64; per conv (six) w [Cout,Cin,3,3] and b [Cout] -> pack of sgdfr_detail_pack_elems() floats.
+ * sgdfr_detail_decode_f32: taps (NULL: off) receives per stage [rows, ...]: the Linear's output [rows,128,8,8], then the five layers'
+ *   outputs, 1941504 floats a row; the layers then write there directly.  workspace of at least sgdfr_detail_workspace_bytes(rows)
+ *   bytes (-1 for rows out of range).  Seven launches plus the finish of a layer that splits K.
+ * sgdfr_detail_upconv_f32: the layer kernel alone: x [rows,Cin,h,w], filter [Cout,Cin,3,3] (transposed into the workspace first), bias
+ *   [Cout] -> y [rows,Cout,up ? 2h : h,up ? 2w : w] = lrelu(conv3x3(up ? upsample2x(x) : x) + bias, slope); slope = 1: no activation.
+ *   rows 1..4096, Cin and Cout 1..1024, h and w 1..256, at most 2^28 output pixels; workspace of at least
+ *   sgdfr_detail_upconv_workspace_bytes(Cin, Cout) bytes.  One 64-pixel x (Cout <= 16 ? 16 : 64)-channel tile per block; the split-K
+ *   plan follows rows, the sizes and the channel counts only.
+ * UV space.  The layout's table pix_to_face [S,S] int32 (-1: none) and bary [S,S,3] come from sgdfr_shaperender_forward_f32 on the UV
+ *   vertices; faces [F,3] index the V mesh vertices; 13 <= S <= 1024.
+ * sgdfr_detail_world2uv_f32: values [rows,V,3] -> out [rows,3,S,S] = sum_k bary_k values[faces[f][k]], 0 where no face covers.
+ * sgdfr_detail_uvnormals_f32: uv_z [rows,1,S,S], vertices and normals [rows,V,3], mask and fixed_dis [S,S] -> uv_normals [rows,3,S,S]:
+ *   the dense vertex of a texel is P = (uv_v + (uv_z mask) uv_n) + fixed_dis uv_n with uv_v, uv_n = world2uv of the vertices, normals;
+ *   the dense faces are util.generate_triangles(S, S): per quad (y, x), x in [2, S-3), y in [5, S-6), x outermost, the two faces
+ *   (a, c, b), (b, c, d) of a = y S + x, b = a + 1, c = a + S, d = c + 1; the normals follow sgdfr_shaperender_normals_f32's rule over
+ *   them, summed in ascending (face, corner) order; a texel outside the meshed rectangle gets zeros.  dense_vertices (NULL: off)
+ *   receives P as [rows,S*S,3] (displacement2vertex).  One launch, no atomics.
+ * Deterministic, no host synchronisation, everything on `stream`. */
+int64_t sgdfr_detail_pack_elems(void);
+int64_t sgdfr_detail_workspace_bytes(int rows);
+int64_t sgdfr_detail_upconv_workspace_bytes(int Cin, int Cout);
+int sgdfr_detail_prepack_f32(const float* const* params, float* pack, void* stream);
+int sgdfr_detail_decode_f32(const float* latent, int rows, const float* pack, float out_scale, float* uv_z, float* taps, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+int sgdfr_detail_upconv_f32(const float* x, const float* w, const float* bias, int rows, int Cin, int Cout, int h, int wd, float slope, int up,
+                            float* y, void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_detail_world2uv_f32(const float* values, int rows, int V, const int* faces, int F, const int* pix_to_face, const float* bary, int S,
+                              float* out, void* stream);
+int sgdfr_detail_uvnormals_f32(const float* uv_z, const float* vertices, const float* normals, int rows, int V, const int* faces, int F,
+                               const int* pix_to_face, const float* bary, const float* mask, const float* fixed_dis, int S, float* uv_normals,
+                               float* dense_vertices, void* stream);
 
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio

@@ -13,6 +13,12 @@
 // No global bins, no atomics, a fixed face order: the result does not depend on scheduling.  All 256 threads read the same LDS record
 // at the same time (three ds_read_b128 of one address: a broadcast, no bank conflict).
 //
+// sgdfr_shaperender_detail_f32 is the same five launches with raster_kernel<true>: one rasterisation serves the smooth panel and the
+// detail panel, whose shading normal is the UV normal map sampled at the pixel's interpolated UV coordinate (grid_sample rules).  The
+// reference renders three times and adds z_offset = 10 to the caller's projected vertices in place each time (renderer.py:255); the
+// projection is orthographic, so a constant shift of z changes no coverage, no barycentric and no depth order, and every |z| < 10
+// stays in front of the z >= 0 cut whether 10, 20 or 30 was added: z_offset stays 10 here and no argument is modified.
+//
 // Floating-point contraction is OFF for the whole file: coverage is a sign test on differences of products, and the tests compare
 // it with a restatement that does not fuse.
 #include <math.h>
@@ -175,10 +181,41 @@ struct RasterOut {
     float* bary;             // [B,S,S,3] or NULL
 };
 
+// the detail panel's inputs and outputs (sgdfr_shaperender_detail_f32); unused by raster_kernel<false>
+struct DetailIO {
+    const float* face_uv;    // [F,3,2]
+    const float* uv_normals; // [B,3,Su,Su]
+    int Su;
+    float* shape_detail;     // [B,3,S,S] or NULL
+    float* grid;             // [B,S,S,2] or NULL
+    float* normal_images;    // [B,3,S,S] or NULL
+};
+
+// F.grid_sample(bilinear, zeros, align_corners=False) of one [3,Su,Su] map at g: a neighbour outside the map adds nothing
+__device__ __forceinline__ void sample_uv(const float* __restrict__ map, int Su, float gx, float gy, float (&r)[3]) {
+    const float ix = ((gx + 1.0f) * (float)Su - 1.0f) * 0.5f, iy = ((gy + 1.0f) * (float)Su - 1.0f) * 0.5f;
+    const float fx = floorf(ix), fy = floorf(iy);
+    const float ax = ix - fx, ay = iy - fy, bx = (fx + 1.0f) - ix, by = (fy + 1.0f) - iy;
+    r[0] = r[1] = r[2] = 0.f;
+    // a coordinate that is not finite or far outside fails every test below (the casts are then never made)
+    if (!(fx >= -1.0f && fx < (float)Su && fy >= -1.0f && fy < (float)Su)) return;
+    const int x0 = (int)fx, y0 = (int)fy;
+    const size_t plane = (size_t)Su * Su;
+    const float w[4] = {bx * by, ax * by, bx * ay, ax * ay};      // nw, ne, sw, se
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x0 + (k & 1), y = y0 + (k >> 1);
+        if (x < 0 || x >= Su || y < 0 || y >= Su) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] += map[c * plane + (size_t)y * Su + x] * w[k];
+    }
+}
+
+template <bool DETAIL>
 __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restrict__ rec, const ushort4* __restrict__ box, int F, int S, int V,
                                                         const int* __restrict__ faces, const float* __restrict__ wn,
                                                         const float* __restrict__ tz, const float* __restrict__ lights, int light_rows, int L,
-                                                        const float* __restrict__ background, int gan_range, RasterOut out) {
+                                                        const float* __restrict__ background, int gan_range, RasterOut out, DetailIO det) {
     __shared__ float4 s_rec[kChunk][3];
     __shared__ float s_light[kMaxLights][6];
     __shared__ int s_wave[kChunk / kWave];
@@ -187,7 +224,7 @@ __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restric
     const int j = tx0 + (t & (kTile - 1)), i = ty0 + t / kTile;
     const bool live = j < S && i < S;
     const float px = __fdiv_rn((float)(2 * j + 1), (float)S) - 1.0f, py = __fdiv_rn((float)(2 * i + 1), (float)S) - 1.0f;
-    if (out.shape && t < L) {
+    if ((DETAIL || out.shape) && t < L) {
         // F.normalize(direction, eps=1e-12) and the intensities of this image's light t
         const float* l = lights + ((size_t)(light_rows == 1 ? 0 : b) * L + t) * 6;
         const float n = fmaxf(sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]), 1e-12f);
@@ -254,8 +291,9 @@ __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restric
         out.bary[pix * 3 + 1] = covered ? w1 : -1.0f;
         out.bary[pix * 3 + 2] = covered ? w2 : -1.0f;
     }
-    if (!out.shape) return;
+    if (!DETAIL && !out.shape) return;
     float shade[3] = {0.f, 0.f, 0.f}, albedo = 0.f, a = 0.f;
+    float dshade[3] = {0.f, 0.f, 0.f}, dn[3] = {0.f, 0.f, 0.f}, gx = 0.f, gy = 0.f;
     if (covered) {
         const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];      // in range: setup skipped the others
         const float* n = wn + (size_t)b * V * 3;
@@ -270,17 +308,42 @@ __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restric
             shade[0] += d * s_light[l][3], shade[1] += d * s_light[l][4], shade[2] += d * s_light[l][5];
         }
         a = tzp < kFrontZ ? 1.0f : 0.0f;
+        if constexpr (DETAIL) {
+            // ops['grid'] and the UV normal map sampled there: the detail panel's shading normal (covered = 1 here)
+            const float* uv = det.face_uv + (size_t)best * 6;
+            gx = w0 * uv[0] + w1 * uv[2] + w2 * uv[4];
+            gy = w0 * uv[1] + w1 * uv[3] + w2 * uv[5];
+            sample_uv(det.uv_normals + (size_t)b * 3 * det.Su * det.Su, det.Su, gx, gy, dn);
+            for (int l = 0; l < L; ++l) {
+                const float d = fminf(fmaxf(dn[0] * s_light[l][0] + dn[1] * s_light[l][1] + dn[2] * s_light[l][2], 0.0f), 1.0f);
+                dshade[0] += d * s_light[l][3], dshade[1] += d * s_light[l][4], dshade[2] += d * s_light[l][5];
+            }
+        }
+    }
+    if constexpr (DETAIL) {
+        if (det.grid) det.grid[pix * 2] = gx, det.grid[pix * 2 + 1] = gy;
     }
     if (out.alpha) out.alpha[pix] = a;
     const size_t plane = (size_t)S * S;
     const size_t o = (size_t)b * 3 * plane + (size_t)i * S + j;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float shading = __fdiv_rn(shade[c], (float)L);
         const float bg = background ? background[o + c * plane] : 0.0f;
-        float v = albedo * shading * a + bg * (1.0f - a);
-        if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
-        out.shape[o + c * plane] = v;
+        if (!DETAIL || out.shape) {
+            const float shading = __fdiv_rn(shade[c], (float)L);
+            float v = albedo * shading * a + bg * (1.0f - a);
+            if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
+            out.shape[o + c * plane] = v;
+        }
+        if constexpr (DETAIL) {
+            if (det.normal_images) det.normal_images[o + c * plane] = dn[c];
+            if (det.shape_detail) {
+                const float shading = __fdiv_rn(dshade[c], (float)L);
+                float v = albedo * shading * a + bg * (1.0f - a);
+                if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
+                det.shape_detail[o + c * plane] = v;
+            }
+        }
     }
 }
 
@@ -307,17 +370,16 @@ extern "C" int sgdfr_shaperender_normals_f32(const float* vertices, int rows, in
     return launch_normals(vertices, rows, V, faces, F, csr_offsets, csr_entries, 0, normals, as_stream(stream));
 }
 
-extern "C" int sgdfr_shaperender_forward_f32(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V,
-                                             const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S,
-                                             const float* lights, int light_rows, int L, const float* background, int gan_range,
-                                             float* shape, float* alpha, int* pix_to_face, float* zbuf, float* bary, void* workspace,
-                                             int64_t workspace_bytes, void* stream) {
+static int forward(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V, const int* faces, int F,
+                   const int* csr_offsets, const int* csr_entries, int S, const float* lights, int light_rows, int L, const float* background,
+                   int gan_range, float* shape, float* alpha, int* pix_to_face, float* zbuf, float* bary, const DetailIO* det, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
     SGDFR_REQUIRE(faces, "shaperender_forward: null faces");
     SGDFR_REQUIRE(sizes_ok(rows, V, F), "shaperender_forward: rows=%d V=%d F=%d (rows 1..4096, V and F 1..2^24)", rows, V, F);
     SGDFR_REQUIRE(S >= 1 && S <= kMaxSize, "shaperender_forward: size=%d (1..%d)", S, kMaxSize);
     SGDFR_REQUIRE((projected != nullptr) != (cam != nullptr), "shaperender_forward: exactly one of projected / cam");
     SGDFR_REQUIRE(!cam || vertices, "shaperender_forward: cam needs the world vertices");
-    const bool shade = shape != nullptr;
+    const bool shade = shape != nullptr || det != nullptr;
     if (shade) {
         SGDFR_REQUIRE(vertices && csr_offsets && csr_entries && lights, "shaperender_forward: shading needs vertices, the vertex table and lights");
         SGDFR_REQUIRE(L >= 1 && L <= kMaxLights, "shaperender_forward: %d lights (1..%d)", L, kMaxLights);
@@ -341,7 +403,33 @@ extern "C" int sgdfr_shaperender_forward_f32(const float* vertices, const float*
     if (check_launch("shaperender setup_kernel")) return 1;
     RasterOut out{shape, alpha, pix_to_face, zbuf, bary};
     const int tiles = (S + kTile - 1) / kTile;
-    raster_kernel<<<dim3(tiles, tiles, rows), kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L, background,
-                                                              gan_range, out);
+    if (det)
+        raster_kernel<true><<<dim3(tiles, tiles, rows), kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L,
+                                                                        background, gan_range, out, *det);
+    else
+        raster_kernel<false><<<dim3(tiles, tiles, rows), kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L,
+                                                                         background, gan_range, out, DetailIO{});
     return check_launch("shaperender raster_kernel");
+}
+
+extern "C" int sgdfr_shaperender_forward_f32(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V,
+                                             const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S,
+                                             const float* lights, int light_rows, int L, const float* background, int gan_range,
+                                             float* shape, float* alpha, int* pix_to_face, float* zbuf, float* bary, void* workspace,
+                                             int64_t workspace_bytes, void* stream) {
+    return forward(vertices, projected, cam, z_offset, rows, V, faces, F, csr_offsets, csr_entries, S, lights, light_rows, L, background,
+                   gan_range, shape, alpha, pix_to_face, zbuf, bary, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgdfr_shaperender_detail_f32(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V,
+                                            const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S,
+                                            const float* lights, int light_rows, int L, const float* background, int gan_range,
+                                            const float* face_uv, const float* uv_normals, int Su, float* shape, float* shape_detail,
+                                            float* grid, float* detail_normal_images, float* alpha, int* pix_to_face, float* zbuf, float* bary,
+                                            void* workspace, int64_t workspace_bytes, void* stream) {
+    SGDFR_REQUIRE(face_uv && uv_normals, "shaperender_detail: null face_uv or uv_normals");
+    SGDFR_REQUIRE(Su >= 1 && Su <= kMaxSize, "shaperender_detail: uv_size=%d (1..%d)", Su, kMaxSize);
+    const DetailIO det{face_uv, uv_normals, Su, shape_detail, grid, detail_normal_images};
+    return forward(vertices, projected, cam, z_offset, rows, V, faces, F, csr_offsets, csr_entries, S, lights, light_rows, L, background,
+                   gan_range, shape, alpha, pix_to_face, zbuf, bary, &det, workspace, workspace_bytes, stream);
 }

@@ -3,8 +3,10 @@ models/resnet.py, of the crop in datasets/datasets.py TestData.get_image_tensor,
 (deca.py:150-165) and of DECA_model.extract_DECA_params / generic.calculate_shapemodel.
 
     E = ResnetEncoder(outsize=236); E.load_state_dict(ckpt['E_flame']); E = E.cuda().eval()
+    E_detail = ResnetEncoder(outsize=128); E_detail.load_state_dict(ckpt['E_detail']); E_detail = E_detail.cuda().eval()
     M = crop_matrix(bbox, (H, W))                         # [B,2,3] from [B,4] 'kpt68' boxes [left, top, right, bottom]
     code = encode(E, images, M)                           # {'shape','tex','exp','pose','cam','light' [B,9,3],'images' [B,3,224,224]}
+    code = encode(E, images, M, E_detail=E_detail)        # ... and 'detail' [B,128], from the same crop (detail.decode_detail takes it)
     params, angles = calculate_shapemodel(E, images, M)   # {'pose','alpha_exp','alpha_shp','cam'}, [B,3] degrees
 
 `ResnetEncoder` has the module layout and state-dict keys of the reference's (deca_model.tar's 'E_flame' loads unchanged) and
@@ -16,7 +18,13 @@ when the images need no gradient.  All 53 BatchNorms are folded into filters + b
 version; the device pack (forward and input-gradient weights, ~2 x 102 MB) is rebuilt whenever a parameter's storage or version
 changes.  The 'kpt68' boxes come in as numbers: landmarks.get_landmarks -> landmarks.kpt68_boxes computes them on the device from the
 caller's face boxes (the S3FD face detector itself stays with the caller), and a row the detector failed on is the caller's
-business (the reference zeroes its coefficients and sets its angles to -180).  E_detail is not built.
+business (the reference zeroes its coefficients and sets its angles to -180).
+
+E_detail is the same network with a 128-row last layer (encoders.ResnetEncoder(outsize=128)): ResnetEncoder(outsize=128) loads
+deca_model.tar's 'E_detail' unchanged and runs on the same kernels, whose output width of 236 is compiled in: `folded()` pads the last
+Linear with zero rows to 236, `forward` / `run` return the first 128 columns, and the angles the kernel computes from the padded
+columns mean nothing and are dropped by `encode`.  The detail code is forward only: it carries no gradient to the images.  Other
+widths (and any last_op) have no kernels.
 """
 from collections import OrderedDict
 
@@ -27,6 +35,7 @@ from . import _native as N
 from .packs import PackedWeights, views
 
 OUTSIZE = 236
+DETAIL_OUTSIZE = 128                                      # n_detail (decalib/utils/config.py)
 CROP = 224
 SCALE = 1.25
 PARAM_LIST = (('shape', 100), ('tex', 50), ('exp', 50), ('pose', 6), ('cam', 3), ('light', 27))   # decalib/utils/config.py:34-40
@@ -71,7 +80,8 @@ class _ResNet(nn.Module):
 
 
 class ResnetEncoder(PackedWeights, nn.Module):
-    """encoders.ResnetEncoder(outsize=236): weights only.  forward(images, M) -> [B,236] parameters on the HIP kernels."""
+    """encoders.ResnetEncoder(outsize=236) (E_flame) or (outsize=128) (E_detail): weights only.  forward(images, M) -> [B,outsize]
+    parameters on the HIP kernels."""
     PREPACK, PACK_ELEMS, PARAMS = 'sgdfr_deca_prepack_f32', 'sgdfr_deca_pack_elems', N.DECA_PARAMS
     TRAIN_ERROR = ('ResnetEncoder: the HIP kernels run the encoder in eval mode only (running BatchNorm statistics); '
                    'call .eval()')
@@ -79,10 +89,11 @@ class ResnetEncoder(PackedWeights, nn.Module):
                   'requires_grad=False')
 
     def __init__(self, outsize=OUTSIZE, last_op=None):
-        if outsize != OUTSIZE or last_op is not None:
-            raise NotImplementedError('ResnetEncoder: only outsize=236 without last_op has HIP kernels (got %r, %r); E_detail is '
-                                      'not built' % (outsize, last_op))
+        if outsize not in (OUTSIZE, DETAIL_OUTSIZE) or last_op is not None:
+            raise NotImplementedError('ResnetEncoder: only outsize=236 (E_flame) and outsize=128 (E_detail) without last_op have HIP '
+                                      'kernels (got %r, %r)' % (outsize, last_op))
         super().__init__()
+        self.outsize = outsize
         self.encoder = _ResNet()
         self.layers = nn.Sequential(nn.Linear(2048, 1024), nn.ReLU(), nn.Linear(1024, outsize))
         for p in self.parameters():
@@ -91,7 +102,8 @@ class ResnetEncoder(PackedWeights, nn.Module):
     # ---- weights
     def folded(self, dtype=torch.float32):
         """The 134 tensors sgdfr_deca_prepack_f32 takes (None for the projection of an identity block), every BatchNorm folded
-        in fp64 on the parameters' device, returned in `dtype`."""
+        in fp64 on the parameters' device, returned in `dtype`.  The last Linear always has the kernels' 236 rows: rows beyond
+        `outsize` are zero."""
         def fold(conv, bn):
             s = bn.weight.detach().double() * torch.rsqrt(bn.running_var.detach().double() + bn.eps)
             w = conv.weight.detach().double() * s.view(-1, 1, 1, 1)
@@ -110,7 +122,11 @@ class ResnetEncoder(PackedWeights, nn.Module):
             else:
                 out += [None, None]
         for lin in (self.layers[0], self.layers[2]):
-            out += [lin.weight.detach().double(), lin.bias.detach().double()]
+            w, b = lin.weight.detach().double(), lin.bias.detach().double()
+            if lin is self.layers[2] and w.shape[0] < OUTSIZE:
+                w = torch.cat([w, w.new_zeros(OUTSIZE - w.shape[0], w.shape[1])])
+                b = torch.cat([b, b.new_zeros(OUTSIZE - b.shape[0])])
+            out += [w, b]
         return [None if v is None else v.to(dtype).contiguous() for v in out]
 
     def forward(self, images, M):
@@ -241,10 +257,17 @@ def _check_inputs(images, M):
 
 
 def run(E, images, M):
-    """(parameters [B,236], angles [B,3] degrees, crop [B,3,224,224]) of one pass; the parameters are differentiable to images."""
+    """(parameters [B,236], angles [B,3] degrees, crop [B,3,224,224]) of one pass; the parameters are differentiable to images.
+    For E_detail (outsize 128): the [B,128] detail code, forward only, and angles that mean nothing."""
     E.check()
     _check_inputs(images, M)
     x = N.f32c(images)
+    if E.outsize != OUTSIZE:
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError('ResnetEncoder(outsize=%d): the detail code has no gradient to the images; call it under '
+                               'torch.no_grad() or on detached images' % E.outsize)
+        params, angles, crop, _, _ = _forward(E.packed(), x, N.f32c(M.detach()), False)
+        return params[:, :E.outsize], angles, crop
     save = torch.is_grad_enabled() and x.requires_grad      # nothing is kept for a forward without a gradient
     return _DecaFn.apply(x, E.packed(), N.f32c(M.detach()), save)
 
@@ -307,11 +330,18 @@ def split_parameters(params):
     return code
 
 
-def encode(E, images, M):
+def encode(E, images, M, E_detail=None):
     """DECA.encode (deca.py:150-165) for a batch of GAN-range images and their crop matrices: {'shape' [B,100], 'tex' [B,50],
-    'exp' [B,50], 'pose' [B,6], 'cam' [B,3], 'light' [B,9,3], 'images' [B,3,224,224] (the crop in [0,1])}."""
+    'exp' [B,50], 'pose' [B,6], 'cam' [B,3], 'light' [B,9,3], 'images' [B,3,224,224] (the crop in [0,1])}; with E_detail
+    (ResnetEncoder(outsize=128)) also 'detail' [B,128] from the same crop, which carries no gradient."""
+    if E_detail is not None and (not isinstance(E_detail, ResnetEncoder) or E_detail.outsize != DETAIL_OUTSIZE):
+        raise ValueError('encode: E_detail must be a ResnetEncoder(outsize=%d)' % DETAIL_OUTSIZE)
+    if E.outsize != OUTSIZE:
+        raise ValueError('encode: E must be a ResnetEncoder(outsize=%d), got outsize=%d' % (OUTSIZE, E.outsize))
     params, _, crop = run(E, images, M)
     code = split_parameters(params)
+    if E_detail is not None:
+        code['detail'] = run(E_detail, images.detach(), M)[0]
     code['images'] = crop
     return code
 

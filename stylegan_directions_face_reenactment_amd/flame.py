@@ -265,6 +265,14 @@ def shape_images(flame, codedict, size=224, images=None, gan_range=False):
         return render_shape(verts, topology(flame), cam=cam, size=size, images=images, gan_range=gan_range)['shape']
 
 
+def shape_detail_images(flame, D_detail, layout, codedict, size=224, images=None, gan_range=False):
+    """The `shape_detail_images` of DECA.decode_deca (deca.py:189): shape_images with the shading normal sampled from the detail normal
+    map that D_detail (detail.DetailDecoder) and the layout (detail.UvLayout) give for codedict['detail'] -> [B,3,size,size].
+    detail.decode_detail returns both panels and the maps from one pass."""
+    from .detail import decode_detail
+    return decode_detail(flame, D_detail, layout, codedict, size=size, images=images, gan_range=gan_range)['shape_detail_images']
+
+
 class _ShapeLossFn(torch.autograd.Function):
     """Both decodes as one batch, the three terms and their cotangents in five launches; backward: two more, for the reenacted set."""
 

@@ -21,6 +21,7 @@ from . import _native as N
 DEFAULT_LIGHTS = tuple((x, y, z, 1.7, 1.7, 1.7) for x, y, z in ((-1, 1, 1), (1, 1, 1), (-1, -1, 1), (1, -1, 1), (0, 0, 1)))
 Z_OFFSET = 10.0                                     # renderer.py:255
 _WANT = ('shape', 'alpha', 'pix_to_face', 'zbuf', 'bary')
+_WANT_DETAIL = ('shape_detail', 'grid', 'detail_normal_images')      # with layout and detail_normals only
 
 
 class MeshTopology:
@@ -136,7 +137,8 @@ def _default_lights(device):
     return _LIGHTS[key]
 
 
-def render_shape(vertices, topo, cam=None, projected=None, size=224, images=None, lights=None, gan_range=False, want=('shape',)):
+def render_shape(vertices, topo, cam=None, projected=None, size=224, images=None, lights=None, gan_range=False, want=('shape',),
+                 layout=None, detail_normals=None):
     """SRenderY.render_shape: world vertices [B,V,3] and exactly one of cam [B,3] = (s, tx, ty) (projected here as DECA.decode
     does: batch_orth_proj, then y and z negated) and projected [B,V,3] (trans_verts) -> a dict with 'shape' [B,3,S,S] and whatever
     else `want` names of 'alpha' [B,1,S,S], 'pix_to_face' [B,S,S] int32, 'zbuf' [B,S,S], 'bary' [B,S,S,3].
@@ -144,11 +146,22 @@ def render_shape(vertices, topo, cam=None, projected=None, size=224, images=None
     images: a background [B,3,S,S] (None: black).  lights: [1 or B, L <= 8, 6] = direction, intensity (None: the reference's five
     at 1.7).  'shape' is in the reference's value range, not clamped (it can exceed 1); gan_range=True gives clamp(shape, 0, 1) * 2 - 1,
     the [-1,1] range a float panel of video_frames_px expects.  The reference adds 10 to the z of the caller's projected vertices in
-    place; here no argument is modified."""
+    place; here no argument is modified.
+
+    layout (a detail.UvLayout of this mesh) and detail_normals (the UV normal map [B,3,Su,Su] of detail.detail_normals), both or
+    neither: `want` may then also name 'shape_detail' [B,3,S,S] (render_shape(..., detail_normal_images=...) of deca.py:189: the same
+    expression with the shading normal sampled from the map), 'grid' [B,S,S,2] (ops['grid']) and 'detail_normal_images' [B,3,S,S],
+    all from the one rasterisation; 'shape' keeps the bits it has without them."""
     who = 'render_shape'
     _check_topology(who, topo)
     want = (want,) if isinstance(want, str) else tuple(want)
-    if 'shape' not in want or any(w not in _WANT for w in want):
+    if (layout is None) != (detail_normals is None):
+        raise RuntimeError('%s: layout and detail_normals must be given together' % who)
+    detail = layout is not None
+    if detail:
+        if 'shape' not in want or any(w not in _WANT + _WANT_DETAIL for w in want):
+            raise RuntimeError("%s: want must name 'shape' and any of %s, got %r" % (who, _WANT[1:] + _WANT_DETAIL, want))
+    elif 'shape' not in want or any(w not in _WANT for w in want):
         raise RuntimeError("%s: want must name 'shape' and any of %s, got %r" % (who, _WANT[1:], want))
     if (cam is None) == (projected is None):
         raise RuntimeError('%s: exactly one of cam and projected must be given' % who)
@@ -180,7 +193,21 @@ def render_shape(vertices, topo, cam=None, projected=None, size=224, images=None
         if lights.ndim != 3 or lights.shape[0] not in (1, B) or not 1 <= lights.shape[1] <= N.SHAPERENDER_MAX_LIGHTS or lights.shape[2] != 6:
             raise RuntimeError('%s: expected lights of shape [1 or %d, 1..%d, 6], got %s' % (who, B, N.SHAPERENDER_MAX_LIGHTS, tuple(lights.shape)))
         lights = N.f32c(lights.detach())
-    if any(t is not None and t.device != dev for t in (cam, projected, images, lights)):
+    if detail:
+        from .detail import UvLayout
+        if not isinstance(layout, UvLayout):
+            raise RuntimeError('%s: layout must be a detail.UvLayout, got %s' % (who, type(layout)))
+        if layout.n_faces != topo.n_faces or layout.n_vertices != topo.n_vertices:
+            raise RuntimeError('%s: the layout is for a mesh of %d vertices and %d faces, topo has %d and %d'
+                               % (who, layout.n_vertices, layout.n_faces, topo.n_vertices, topo.n_faces))
+        if not torch.is_tensor(detail_normals):
+            raise RuntimeError('%s: detail_normals must be a tensor, got %s' % (who, type(detail_normals)))
+        N.require_device(detail_normals)
+        Su = layout.uv_size
+        if tuple(detail_normals.shape) != (B, 3, Su, Su):
+            raise RuntimeError('%s: expected detail_normals of shape [%d,3,%d,%d], got %s' % (who, B, Su, Su, tuple(detail_normals.shape)))
+        detail_normals = N.f32c(detail_normals.detach())
+    if any(t is not None and t.device != dev for t in (cam, projected, images, lights, detail_normals)):
         raise RuntimeError('%s: all tensors must live on the vertices\' device %s' % (who, dev))
     faces, offsets, entries = topo.tables(dev)
     out = {'shape': torch.empty((B, 3, size, size), dtype=torch.float32, device=dev)}
@@ -189,6 +216,17 @@ def render_shape(vertices, topo, cam=None, projected=None, size=224, images=None
         if name in want:
             out[name] = torch.empty(shape, dtype=dtype, device=dev)
     ws, nbytes = _workspace(B, topo, dev)
+    if detail:
+        for name, shape in (('shape_detail', (B, 3, size, size)), ('grid', (B, size, size, 2)), ('detail_normal_images', (B, 3, size, size))):
+            if name in want:
+                out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        face_uv = layout.tables(dev)[5]
+        N.call('sgdfr_shaperender_detail_f32', N.ptr(v), N.ptr(projected), N.ptr(cam), Z_OFFSET, B, topo.n_vertices, N.ptr(faces), topo.n_faces,
+               N.ptr(offsets), N.ptr(entries), size, N.ptr(lights), lights.shape[0], lights.shape[1], N.ptr(images), int(bool(gan_range)),
+               N.ptr(face_uv), N.ptr(detail_normals), layout.uv_size, N.ptr(out['shape']), N.ptr(out.get('shape_detail')), N.ptr(out.get('grid')),
+               N.ptr(out.get('detail_normal_images')), N.ptr(out.get('alpha')), N.ptr(out.get('pix_to_face')), N.ptr(out.get('zbuf')),
+               N.ptr(out.get('bary')), N.ptr(ws), nbytes, N.stream())
+        return out
     N.call('sgdfr_shaperender_forward_f32', N.ptr(v), N.ptr(projected), N.ptr(cam), Z_OFFSET, B, topo.n_vertices, N.ptr(faces), topo.n_faces,
            N.ptr(offsets), N.ptr(entries), size, N.ptr(lights), lights.shape[0], lights.shape[1], N.ptr(images), int(bool(gan_range)),
            N.ptr(out['shape']), N.ptr(out.get('alpha')), N.ptr(out.get('pix_to_face')), N.ptr(out.get('zbuf')), N.ptr(out.get('bary')),

@@ -235,7 +235,7 @@ def synthetic_arcface_state(seed):
     return out
 
 
-def synthetic_deca_encoder_state(seed):
+def synthetic_deca_encoder_state(seed, outsize=236):
     """Seeded DECA coefficient-encoder state dict in encoders.ResnetEncoder(outsize=236)'s keys (deca.ResnetEncoder): He-scaled
     conv filters N(0, 2/fan_in), BatchNorm statistics near (0, 1), the scale of each bottleneck's last BatchNorm (bn3) and of the
     projection's around 0.5 -- so the residual sums stay O(1) through the 16 bottlenecks --, Linear weights N(0, 1/fan_in) with
@@ -243,7 +243,7 @@ def synthetic_deca_encoder_state(seed):
     from collections import OrderedDict
     from .deca import ResnetEncoder
     out = OrderedDict()
-    for key, t in ResnetEncoder().state_dict().items():
+    for key, t in ResnetEncoder(outsize).state_dict().items():
         shape = tuple(t.shape)
         if key.endswith('num_batches_tracked'):
             out[key] = torch.zeros(shape, dtype=torch.int64)
@@ -261,6 +261,51 @@ def synthetic_deca_encoder_state(seed):
         elif key.endswith('.weight'):                             # BatchNorm scale
             last = '.bn3.' in key or '.downsample.1.' in key
             out[key] = counter_tensor(seed, key, shape, 0.5 if last else 1.0, 0.05 if last else 0.1)
+        else:
+            raise KeyError(key)
+    return out
+
+
+def synthetic_deca_detail_encoder_state(seed):
+    """Seeded E_detail state dict, encoders.ResnetEncoder(outsize=128)'s keys (deca.ResnetEncoder(128)): synthetic_deca_encoder_state
+    with a 128-row last layer.  A key that E_flame has too gets the values it has there at the same seed: pass another seed for an
+    encoder that differs from E_flame."""
+    return synthetic_deca_encoder_state(seed, outsize=128)
+
+
+# synthetic_detail_decoder_state: gain of the last conv's filter on N(0, 1/fan_in).  The five BatchNorms with eps = 0.8 each take a
+# quarter off the spread, which reaches the last conv at 0.17; 64 puts the value in front of tanh at a spread of about 0.7.
+DETAIL_DECODER_LAST_GAIN = 64.0
+
+
+def synthetic_detail_decoder_state(seed):
+    """Seeded D_detail state dict in the keys of decoders.Generator(181, 1, 0.01, 'bilinear') (detail.DetailDecoder): the Linear
+    N(0, 1/fan_in), conv filters N(0, 2/fan_in), biases N(0, 0.05^2), BatchNorm scales near 1 and shifts near 0, running means
+    N(0, 0.1^2) and running variances around 1 floored at 0.3 -- the five BatchNorm2d(C, 0.8) add their eps = 0.8 to those -- and the
+    last conv scaled so that the value in front of tanh has a standard deviation between 0.3 and 1.5 for N(0, 1) latents
+    (scripts/make_golden_detail.py asserts it): tanh is then neither flat nor linear.  8 MB: regenerated from the seed, never stored."""
+    from collections import OrderedDict
+    from .detail import DetailDecoder
+    out = OrderedDict()
+    for key, t in DetailDecoder().state_dict().items():
+        shape = tuple(t.shape)
+        if key.endswith('num_batches_tracked'):
+            out[key] = torch.zeros(shape, dtype=torch.int64)
+        elif key.endswith('running_var'):
+            v = counter_normal(seed, key, int(np.prod(shape))) * 0.2 + 1.0
+            out[key] = torch.from_numpy(np.maximum(v, 0.3).astype(np.float32).reshape(shape))
+        elif key.endswith('running_mean'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.1)
+        elif len(shape) == 4:
+            last = key == 'conv_blocks.21.weight'
+            gain = DETAIL_DECODER_LAST_GAIN if last else 2.0
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(gain / (shape[1] * shape[2] * shape[3]))))
+        elif len(shape) == 2:
+            out[key] = counter_tensor(seed, key, shape, 0.0, float(np.sqrt(1.0 / shape[1])))
+        elif key.endswith('.bias'):
+            out[key] = counter_tensor(seed, key, shape, 0.0, 0.05)
+        elif key.endswith('.weight'):                             # BatchNorm scale
+            out[key] = counter_tensor(seed, key, shape, 1.0, 0.1)
         else:
             raise KeyError(key)
     return out
