@@ -1106,6 +1106,58 @@ int sgdfr_detail_uvnormals_f32(const float* uv_z, const float* vertices, const f
                                const int* pix_to_face, const float* bary, const float* mask, const float* fixed_dis, int S, float* uv_normals,
                                float* dense_vertices, void* stream);
 
+/* DECA's texture side (libs/DECA/decalib/models/FLAME.py:216-262 FLAMETex, utils/renderer.py:121-206 SRenderY.forward and add_SHlight,
+ * 295-329 render_depth / render_normal, deca.py:143-148 visofp and 180-199), csrc/texture.hip, csrc/shaperender.hip, csrc/flame.hip.
+ * Forward only.
+ * FLAMETex: albedo [rows,3,uv,uv] = (mean + basis . code) at the source size Hs x Ws x 3, nearest-neighbour resized to uv x uv, channels
+ *   flipped [2,1,0].  1 <= uv <= 1024, 1 <= n_tex <= 200, Hs and Ws 1..4096, rows 1..4096.
+ * sgdfr_flametex_prepack_f32: params = host array of 4 device pointers: texture_mean [Hs*Ws*3], texture_basis [Hs*Ws*3][n_tex], and the
+ *   source row of every output row and source column of every output column, int32 [uv] each (F.interpolate's nearest rule, evaluated
+ *   on the host) -> pack of sgdfr_flametex_pack_elems(uv, n_tex) floats: mean [3][uv][uv], then basis [n_tex][3][uv][uv], kept texels
+ *   only, channels already flipped.
+ * sgdfr_flametex_forward_f32: code [rows,n_tex] -> albedo = mean + sum_k basis_k code[row][k], k ascending, one fmaf each: a row's bits
+ *   do not depend on the batch.  One launch; the pack is streamed from memory once per group of 32 rows.
+ * sgdfr_shaperender_texture_f32: SRenderY.forward from the rasterisation of sgdfr_shaperender_forward_f32 (same vertices / projected /
+ *   cam / z_offset arguments and workspace).  face_uv [F,3,2]; albedo [rows,3,Su,Su] (NULL without images and albedo_images);
+ *   sh_lights [rows,9,3] or NULL; sh_constants: HOST array of the 9 factors of renderer.py:114-119.  With w the barycentrics of the covering face and all attributes 0 where none covers,
+ *   every output may be NULL:
+ *   grid [rows,S,S,2] as sgdfr_shaperender_detail_f32 writes it, bit for bit; alpha_images [rows,1,S,S] = 1 where a face covers (no
+ *   front-facing mask); pos_mask [rows,1,S,S] = 1 where the interpolated z of the projected vertices' normals is < -0.05;
+ *   normal_images [rows,3,S,S] = alpha * interpolated world normal (not renormalised); shading_images [rows,3,S,S] = sum_k
+ *   sh_lights[k][c] (basis_k(n) constant_k), k ascending, basis = (1, x, y, z, xy, xz, yz, x^2 - y^2, 3 z^2 - 1) of the interpolated
+ *   normal -- NOT masked: c0 L0 - c8 L8 where no face covers -- and 0 without sh_lights; albedo_images [rows,3,S,S] = alpha *
+ *   bilinear(albedo, grid) (the grid_sample rules above); images = albedo_images * shading_images (albedo_images without sh_lights);
+ *   normals and transformed_normals [rows,V,3]: the vertex normals of the world and of the projected vertices; pix_to_face, zbuf, bary
+ *   as above.  Five launches, six with transformed_normals.
+ * sgdfr_shaperender_attr_f32: values [rows,V,D], D 1..3, interpolated over the rasterisation of `projected` (z + z_offset) -> out
+ *   [rows,D,S,S], 0 where no face covers (render_normal; render_depth with the normalised depth as the value).  Three launches.
+ * sgdfr_texture_uv_f32: the UV texture pass in one launch over [rows,S,S]: uv_shading = add_SHlight(uv_normals [rows,3,S,S], light
+ *   [rows,9,3]); uv_texture = albedo * uv_shading (albedo [rows,3,S,S], NULL: no texture model); uv_pverts = world2uv(trans_verts
+ *   [rows,V,3]) through the layout's table (pix_to_face [S,S], bary [S,S,3], faces [F,3]), 0 where no face covers; uv_gt = bilinear(images
+ *   [rows,3,H,W], uv_pverts.xy), so an uncovered texel samples the image centre; uv_texture_gt = uv_gt mask + (uv_texture, or 1 without
+ *   albedo) (1 - mask) 0.7 with mask [S,S].  Every output may be NULL; S 1..1024, H and W 1..4096.
+ * sgdfr_flame_visofp_f32: values [rows,n_vertices,3] gathered at n landmarks (corners int32 [n,3] vertex indices, bary [n,3]) ->
+ *   vis [rows,n,1] = 1 where the gathered z < threshold; gathered [rows,n,3] (NULL: off).
+ * Deterministic, no host synchronisation, everything on `stream`. */
+int64_t sgdfr_flametex_pack_elems(int uv, int n_tex);
+int sgdfr_flametex_prepack_f32(const void* const* params, int Hs, int Ws, int uv, int n_tex, float* pack, void* stream);
+int sgdfr_flametex_forward_f32(const float* code, int rows, const float* pack, int uv, int n_tex, float* albedo, void* stream);
+int sgdfr_shaperender_texture_f32(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V,
+                                  const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S, const float* sh_lights,
+                                  const float* sh_constants, const float* face_uv, const float* albedo, int Su, float* images,
+                                  float* albedo_images, float* alpha_images, float* pos_mask, float* shading_images, float* grid,
+                                  float* normal_images, float* normals, float* transformed_normals, int* pix_to_face, float* zbuf, float* bary,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+int sgdfr_shaperender_attr_f32(const float* projected, float z_offset, int rows, int V, const int* faces, int F, int S, const float* values,
+                               int D, float* out, int* pix_to_face, float* zbuf, float* bary, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+int sgdfr_texture_uv_f32(const float* albedo, const float* uv_normals, const float* light, const float* sh_constants, const float* trans_verts,
+                         const float* images, int rows, int V, int H, int W, const int* faces, int F, const int* pix_to_face, const float* bary,
+                         const float* mask, int S, float* uv_shading, float* uv_texture, float* uv_texture_gt, float* uv_pverts, float* uv_gt,
+                         void* stream);
+int sgdfr_flame_visofp_f32(const float* values, int rows, int n_vertices, const int* corners, const float* bary, int n, float threshold,
+                           float* vis, float* gathered, void* stream);
+
 /* Measurement aid (csrc/probe.hip; no reference counterpart): the rate v_mfma_f32_32x32x16_{f16,bf16} sustains on THIS device,
  * in 16-bit TFLOP/s -- arith SGDFR_SPLIT_FP16/BF16; lds_fragments 1: operands re-read from LDS at the split conv's ratio
  * (8 ds_read_b128 per 12 MFMAs), 0: register operands; random_operands 1: random mantissas, 0: zeros.  The chip clocks to its

@@ -267,6 +267,18 @@ SIGNATURES['sgdfr_detail_uvnormals_f32'] = [_c_f32p, _c_f32p, _c_f32p, _i, _i, _
 DETAIL_PARAMS = 14      # pointers sgdfr_detail_prepack_f32 takes
 DETAIL_LATENT, DETAIL_UV_SIZE = 181, 256                    # csrc/detail.hip kLatent, kUvSize
 DETAIL_UV_MIN, DETAIL_UV_MAX = 13, 1024                     # csrc/detail.hip kUvMin, kUvMax
+_host_fp = ctypes.POINTER(ctypes.c_float)  # float* on the HOST
+SIGNATURES['sgdfr_flametex_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _i, _i, _i, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_flametex_forward_f32'] = [_c_f32p, _i, _c_f32p, _i, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_shaperender_texture_f32'] = ([_c_f32p, _c_f32p, _c_f32p, _f, _i, _i, _ip, _i, _ip, _ip, _i, _c_f32p, _host_fp, _c_f32p, _c_f32p,
+                                                _i] + [_c_f32p] * 9 + [_ip, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p])
+SIGNATURES['sgdfr_shaperender_attr_f32'] = [_c_f32p, _f, _i, _i, _ip, _i, _i, _c_f32p, _i, _c_f32p, _ip, _c_f32p, _c_f32p, ctypes.c_void_p, _i64,
+                                            ctypes.c_void_p]
+SIGNATURES['sgdfr_texture_uv_f32'] = ([_c_f32p, _c_f32p, _c_f32p, _host_fp, _c_f32p, _c_f32p, _i, _i, _i, _i, _ip, _i, _ip, _c_f32p, _c_f32p, _i]
+                                      + [_c_f32p] * 5 + [ctypes.c_void_p])
+SIGNATURES['sgdfr_flame_visofp_f32'] = [_c_f32p, _i, _i, _ip, _c_f32p, _i, _f, _c_f32p, _c_f32p, ctypes.c_void_p]
+FLAMETEX_PARAMS = 4     # pointers sgdfr_flametex_prepack_f32 takes
+FLAMETEX_MAX_TEX, FLAMETEX_MAX_UV, FLAMETEX_MAX_SOURCE = 200, 1024, 4096     # csrc/texture.hip kMaxTex, kMaxUv, kMaxSource
 E4E_PARAMS_256 = 423  # pointers sgdfr_e4e_prepack_f32 takes at R = 256 (sgdfr_e4e_param_count(R) in general)
 DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}      # SGDFR_DTYPE_* of the two reference natives
 # measurement-only symbols: bound when present, never required of a production library (bench.py's measured_mfma_ceiling)
@@ -287,6 +299,7 @@ SIZE_QUERIES = {
     'sgdfr_pairloss_workspace_bytes': 1,
     'sgdfr_shaperender_workspace_bytes': 3,
     'sgdfr_detail_pack_elems': 0, 'sgdfr_detail_workspace_bytes': 1, 'sgdfr_detail_upconv_workspace_bytes': 2,
+    'sgdfr_flametex_pack_elems': 2,
 }
 COUNT_QUERIES = ('sgdfr_e4e_style_count', 'sgdfr_e4e_param_count')      # int (int R): a count, or -1 for a resolution out of range
 

@@ -652,6 +652,24 @@ __global__ void __launch_bounds__(256) flame_pose_bwd_kernel(const float* __rest
 
 constexpr int MAX_ROWS = 4096;
 
+// DECA.visofp (deca.py:143-148): the barycentric gather of any per-vertex values at n landmarks (seletec_3d68 of the normals), and
+// z < threshold as 0 / 1.  The landmark launch above reads the decode's saved block, so arbitrary [rows,V,3] values get this one.
+__global__ void __launch_bounds__(256) flame_visofp_kernel(const float* __restrict__ values, int rows, int nv, const int* __restrict__ corners,
+                                                           const float* __restrict__ bary, int n, float threshold, float* __restrict__ vis,
+                                                           float* __restrict__ gathered) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * n) return;
+    const int r = i / n, s = i - r * n;
+    const float* v = values + (int64_t)r * nv * 3;
+    const unsigned i0 = (unsigned)corners[s * 3], i1 = (unsigned)corners[s * 3 + 1], i2 = (unsigned)corners[s * 3 + 2];
+    float p[3] = {0.f, 0.f, 0.f};
+    if (i0 < (unsigned)nv && i1 < (unsigned)nv && i2 < (unsigned)nv)
+        for (int k = 0; k < 3; ++k) p[k] = v[i0 * 3 + k] * bary[s * 3] + v[i1 * 3 + k] * bary[s * 3 + 1] + v[i2 * 3 + k] * bary[s * 3 + 2];
+    vis[i] = p[2] < threshold ? 1.f : 0.f;
+    if (gathered)
+        for (int k = 0; k < 3; ++k) gathered[(int64_t)i * 3 + k] = p[k];
+}
+
 }  // namespace
 
 extern "C" {
@@ -743,6 +761,16 @@ int sgdfr_shape_loss_f32(const float* landmarks2d, const float* trans_verts, int
     hipLaunchKernelGGL(flame_loss_sum_kernel, dim3(1), dim3(64), 0, st, (const float*)part, rows, lambda_shape, lambda_mouth, lambda_eye,
                        loss, terms);
     return check_launch("flame_loss_sum");
+}
+
+int sgdfr_flame_visofp_f32(const float* values, int rows, int n_vertices, const int* corners, const float* bary, int n, float threshold,
+                           float* vis, float* gathered, void* stream) {
+    SGDFR_REQUIRE(values && corners && bary && vis, "flame_visofp: NULL input or output");
+    SGDFR_REQUIRE(rows > 0 && rows <= MAX_ROWS && n_vertices >= 1 && n_vertices <= (1 << 24) && n >= 1 && n <= 4096,
+                  "flame_visofp: rows=%d vertices=%d landmarks=%d (rows 1..%d, vertices 1..2^24, landmarks 1..4096)", rows, n_vertices, n, MAX_ROWS);
+    hipLaunchKernelGGL(flame_visofp_kernel, dim3((rows * n + 255) / 256), dim3(256), 0, as_stream(stream), values, rows, n_vertices, corners,
+                       bary, n, threshold, vis, gathered);
+    return check_launch("flame_visofp");
 }
 
 }  // extern "C"

@@ -19,6 +19,11 @@
 // projection is orthographic, so a constant shift of z changes no coverage, no barycentric and no depth order, and every |z| < 10
 // stays in front of the z >= 0 cut whether 10, 20 or 30 was added: z_offset stays 10 here and no argument is modified.
 //
+// sgdfr_shaperender_texture_f32 is the third instance, raster_kernel<kTexture>: SRenderY.forward (renderer.py:121-191), the albedo map
+// sampled at the pixel's UV coordinate, add_SHlight on the interpolated world normal, the coverage and the z < -0.05 mask of the
+// projected normals.  sgdfr_shaperender_attr_f32 is the fourth, raster_kernel<kAttr>: D <= 3 per-vertex values interpolated, 0 where no
+// face covers (render_normal, render_depth; no normals are computed: three launches).
+//
 // Floating-point contraction is OFF for the whole file: coverage is a sign test on differences of products, and the tests compare
 // it with a restatement that does not fuse.
 #include <math.h>
@@ -191,6 +196,31 @@ struct DetailIO {
     float* normal_images;    // [B,3,S,S] or NULL
 };
 
+// the textured render's inputs and outputs (sgdfr_shaperender_texture_f32); every output may be NULL
+struct TexIO {
+    const float* face_uv;    // [F,3,2]
+    const float* albedo;     // [B,3,Su,Su]
+    int Su;
+    float sh[9];             // renderer.py:114-119, rounded to float once on the host
+    float* images;           // [B,3,S,S]
+    float* albedo_images;    // [B,3,S,S]
+    float* alpha;            // [B,1,S,S]
+    float* pos_mask;         // [B,1,S,S]
+    float* shading;          // [B,3,S,S]
+    float* grid;             // [B,S,S,2]
+    float* normal_images;    // [B,3,S,S]
+};
+
+// the attribute mode (sgdfr_shaperender_attr_f32)
+struct AttrIO {
+    const float* values;     // [B,V,D]
+    int D;                   // 1..3
+    float* out;              // [B,D,S,S]
+};
+
+constexpr int kShape = 0, kDetail = 1, kTexture = 2, kAttr = 3;      // raster_kernel's modes
+constexpr float kPosZ = -0.05f;              // renderer.py:159
+
 // F.grid_sample(bilinear, zeros, align_corners=False) of one [3,Su,Su] map at g: a neighbour outside the map adds nothing
 __device__ __forceinline__ void sample_uv(const float* __restrict__ map, int Su, float gx, float gy, float (&r)[3]) {
     const float ix = ((gx + 1.0f) * (float)Su - 1.0f) * 0.5f, iy = ((gy + 1.0f) * (float)Su - 1.0f) * 0.5f;
@@ -211,11 +241,24 @@ __device__ __forceinline__ void sample_uv(const float* __restrict__ map, int Su,
     }
 }
 
-template <bool DETAIL>
+// SRenderY.add_SHlight at one normal: sum_k coeff[k][c] (basis_k(n) constant_k), k ascending; coeff [9][3]
+__device__ __forceinline__ void sh_light(const float (&c)[9], const float* coeff, float nx, float ny, float nz, float (&r)[3]) {
+    const float basis[9] = {1.0f, nx, ny, nz, nx * ny, nx * nz, ny * nz, nx * nx - ny * ny, 3.0f * (nz * nz) - 1.0f};
+    r[0] = r[1] = r[2] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const float sh = basis[k] * c[k];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) r[ch] += coeff[k * 3 + ch] * sh;
+    }
+}
+
+template <int MODE, typename IO>
 __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restrict__ rec, const ushort4* __restrict__ box, int F, int S, int V,
                                                         const int* __restrict__ faces, const float* __restrict__ wn,
                                                         const float* __restrict__ tz, const float* __restrict__ lights, int light_rows, int L,
-                                                        const float* __restrict__ background, int gan_range, RasterOut out, DetailIO det) {
+                                                        const float* __restrict__ background, int gan_range, RasterOut out, IO det) {
+    constexpr bool DETAIL = MODE == kDetail;
     __shared__ float4 s_rec[kChunk][3];
     __shared__ float s_light[kMaxLights][6];
     __shared__ int s_wave[kChunk / kWave];
@@ -224,7 +267,9 @@ __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restric
     const int j = tx0 + (t & (kTile - 1)), i = ty0 + t / kTile;
     const bool live = j < S && i < S;
     const float px = __fdiv_rn((float)(2 * j + 1), (float)S) - 1.0f, py = __fdiv_rn((float)(2 * i + 1), (float)S) - 1.0f;
-    if ((DETAIL || out.shape) && t < L) {
+    if constexpr (MODE == kTexture) {
+        if (lights && t < 27) (&s_light[0][0])[t] = lights[(size_t)b * 27 + t];       // this image's SH coefficients [9][3]
+    } else if ((DETAIL || (MODE == kShape && out.shape)) && t < L) {
         // F.normalize(direction, eps=1e-12) and the intensities of this image's light t
         const float* l = lights + ((size_t)(light_rows == 1 ? 0 : b) * L + t) * 6;
         const float n = fmaxf(sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]), 1e-12f);
@@ -291,57 +336,96 @@ __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restric
         out.bary[pix * 3 + 1] = covered ? w1 : -1.0f;
         out.bary[pix * 3 + 2] = covered ? w2 : -1.0f;
     }
-    if (!DETAIL && !out.shape) return;
-    float shade[3] = {0.f, 0.f, 0.f}, albedo = 0.f, a = 0.f;
-    float dshade[3] = {0.f, 0.f, 0.f}, dn[3] = {0.f, 0.f, 0.f}, gx = 0.f, gy = 0.f;
-    if (covered) {
-        const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];      // in range: setup skipped the others
-        const float* n = wn + (size_t)b * V * 3;
-        const float* z = tz + (size_t)b * V;
-        const float nx = w0 * n[i0 * 3] + w1 * n[i1 * 3] + w2 * n[i2 * 3];
-        const float ny = w0 * n[i0 * 3 + 1] + w1 * n[i1 * 3 + 1] + w2 * n[i2 * 3 + 1];
-        const float nz = w0 * n[i0 * 3 + 2] + w1 * n[i1 * 3 + 2] + w2 * n[i2 * 3 + 2];
-        const float tzp = w0 * z[i0] + w1 * z[i1] + w2 * z[i2];
-        albedo = (w0 + w1 + w2) * kAlbedo;
-        for (int l = 0; l < L; ++l) {
-            const float d = fminf(fmaxf(nx * s_light[l][0] + ny * s_light[l][1] + nz * s_light[l][2], 0.0f), 1.0f);
-            shade[0] += d * s_light[l][3], shade[1] += d * s_light[l][4], shade[2] += d * s_light[l][5];
+    if constexpr (MODE == kAttr) {
+        float r[3] = {0.f, 0.f, 0.f};
+        if (covered) {
+            const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];
+            const float* a = det.values + (size_t)b * V * det.D;
+            for (int c = 0; c < det.D; ++c) r[c] = w0 * a[i0 * det.D + c] + w1 * a[i1 * det.D + c] + w2 * a[i2 * det.D + c];
         }
-        a = tzp < kFrontZ ? 1.0f : 0.0f;
-        if constexpr (DETAIL) {
-            // ops['grid'] and the UV normal map sampled there: the detail panel's shading normal (covered = 1 here)
+        for (int c = 0; c < det.D; ++c) det.out[((size_t)b * det.D + c) * S * S + (size_t)i * S + j] = r[c];
+    } else if constexpr (MODE == kTexture) {
+        // SRenderY.forward: an uncovered pixel has every attribute 0, so its shading is add_SHlight(0) and everything else 0
+        float n[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f}, sh[3] = {0.f, 0.f, 0.f}, tzp = 0.f, gx = 0.f, gy = 0.f;
+        const float a = covered ? 1.0f : 0.0f;
+        if (covered) {
+            const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];
+            const float* nw = wn + (size_t)b * V * 3;
+            const float* z = tz + (size_t)b * V;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) n[c] = w0 * nw[i0 * 3 + c] + w1 * nw[i1 * 3 + c] + w2 * nw[i2 * 3 + c];
+            tzp = w0 * z[i0] + w1 * z[i1] + w2 * z[i2];
             const float* uv = det.face_uv + (size_t)best * 6;
             gx = w0 * uv[0] + w1 * uv[2] + w2 * uv[4];
             gy = w0 * uv[1] + w1 * uv[3] + w2 * uv[5];
-            sample_uv(det.uv_normals + (size_t)b * 3 * det.Su * det.Su, det.Su, gx, gy, dn);
+            if (det.images || det.albedo_images) sample_uv(det.albedo + (size_t)b * 3 * det.Su * det.Su, det.Su, gx, gy, al);
+        }
+        if (lights) sh_light(det.sh, &s_light[0][0], n[0], n[1], n[2], sh);
+        if (det.grid) det.grid[pix * 2] = gx, det.grid[pix * 2 + 1] = gy;
+        if (det.alpha) det.alpha[pix] = a;
+        if (det.pos_mask) det.pos_mask[pix] = tzp < kPosZ ? 1.0f : 0.0f;
+        const size_t plane = (size_t)S * S;
+        const size_t o = (size_t)b * 3 * plane + (size_t)i * S + j;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (det.images) det.images[o + c * plane] = (lights ? al[c] * sh[c] : al[c]) * a;
+            if (det.albedo_images) det.albedo_images[o + c * plane] = al[c] * a;
+            if (det.shading) det.shading[o + c * plane] = sh[c];
+            if (det.normal_images) det.normal_images[o + c * plane] = n[c] * a;
+        }
+    } else {
+        if (!DETAIL && !out.shape) return;
+        float shade[3] = {0.f, 0.f, 0.f}, albedo = 0.f, a = 0.f;
+        float dshade[3] = {0.f, 0.f, 0.f}, dn[3] = {0.f, 0.f, 0.f}, gx = 0.f, gy = 0.f;
+        if (covered) {
+            const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];      // in range: setup skipped the others
+            const float* n = wn + (size_t)b * V * 3;
+            const float* z = tz + (size_t)b * V;
+            const float nx = w0 * n[i0 * 3] + w1 * n[i1 * 3] + w2 * n[i2 * 3];
+            const float ny = w0 * n[i0 * 3 + 1] + w1 * n[i1 * 3 + 1] + w2 * n[i2 * 3 + 1];
+            const float nz = w0 * n[i0 * 3 + 2] + w1 * n[i1 * 3 + 2] + w2 * n[i2 * 3 + 2];
+            const float tzp = w0 * z[i0] + w1 * z[i1] + w2 * z[i2];
+            albedo = (w0 + w1 + w2) * kAlbedo;
             for (int l = 0; l < L; ++l) {
-                const float d = fminf(fmaxf(dn[0] * s_light[l][0] + dn[1] * s_light[l][1] + dn[2] * s_light[l][2], 0.0f), 1.0f);
-                dshade[0] += d * s_light[l][3], dshade[1] += d * s_light[l][4], dshade[2] += d * s_light[l][5];
+                const float d = fminf(fmaxf(nx * s_light[l][0] + ny * s_light[l][1] + nz * s_light[l][2], 0.0f), 1.0f);
+                shade[0] += d * s_light[l][3], shade[1] += d * s_light[l][4], shade[2] += d * s_light[l][5];
+            }
+            a = tzp < kFrontZ ? 1.0f : 0.0f;
+            if constexpr (DETAIL) {
+                // ops['grid'] and the UV normal map sampled there: the detail panel's shading normal (covered = 1 here)
+                const float* uv = det.face_uv + (size_t)best * 6;
+                gx = w0 * uv[0] + w1 * uv[2] + w2 * uv[4];
+                gy = w0 * uv[1] + w1 * uv[3] + w2 * uv[5];
+                sample_uv(det.uv_normals + (size_t)b * 3 * det.Su * det.Su, det.Su, gx, gy, dn);
+                for (int l = 0; l < L; ++l) {
+                    const float d = fminf(fmaxf(dn[0] * s_light[l][0] + dn[1] * s_light[l][1] + dn[2] * s_light[l][2], 0.0f), 1.0f);
+                    dshade[0] += d * s_light[l][3], dshade[1] += d * s_light[l][4], dshade[2] += d * s_light[l][5];
+                }
             }
         }
-    }
-    if constexpr (DETAIL) {
-        if (det.grid) det.grid[pix * 2] = gx, det.grid[pix * 2 + 1] = gy;
-    }
-    if (out.alpha) out.alpha[pix] = a;
-    const size_t plane = (size_t)S * S;
-    const size_t o = (size_t)b * 3 * plane + (size_t)i * S + j;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float bg = background ? background[o + c * plane] : 0.0f;
-        if (!DETAIL || out.shape) {
-            const float shading = __fdiv_rn(shade[c], (float)L);
-            float v = albedo * shading * a + bg * (1.0f - a);
-            if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
-            out.shape[o + c * plane] = v;
-        }
         if constexpr (DETAIL) {
-            if (det.normal_images) det.normal_images[o + c * plane] = dn[c];
-            if (det.shape_detail) {
-                const float shading = __fdiv_rn(dshade[c], (float)L);
+            if (det.grid) det.grid[pix * 2] = gx, det.grid[pix * 2 + 1] = gy;
+        }
+        if (out.alpha) out.alpha[pix] = a;
+        const size_t plane = (size_t)S * S;
+        const size_t o = (size_t)b * 3 * plane + (size_t)i * S + j;
+    #pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float bg = background ? background[o + c * plane] : 0.0f;
+            if (!DETAIL || out.shape) {
+                const float shading = __fdiv_rn(shade[c], (float)L);
                 float v = albedo * shading * a + bg * (1.0f - a);
                 if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
-                det.shape_detail[o + c * plane] = v;
+                out.shape[o + c * plane] = v;
+            }
+            if constexpr (DETAIL) {
+                if (det.normal_images) det.normal_images[o + c * plane] = dn[c];
+                if (det.shape_detail) {
+                    const float shading = __fdiv_rn(dshade[c], (float)L);
+                    float v = albedo * shading * a + bg * (1.0f - a);
+                    if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
+                    det.shape_detail[o + c * plane] = v;
+                }
             }
         }
     }
@@ -373,14 +457,19 @@ extern "C" int sgdfr_shaperender_normals_f32(const float* vertices, int rows, in
 static int forward(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V, const int* faces, int F,
                    const int* csr_offsets, const int* csr_entries, int S, const float* lights, int light_rows, int L, const float* background,
                    int gan_range, float* shape, float* alpha, int* pix_to_face, float* zbuf, float* bary, const DetailIO* det, void* workspace,
-                   int64_t workspace_bytes, void* stream) {
+                   int64_t workspace_bytes, void* stream, const TexIO* tex = nullptr, float* normals = nullptr, float* tnormals = nullptr,
+                   const AttrIO* attr = nullptr) {
     SGDFR_REQUIRE(faces, "shaperender_forward: null faces");
     SGDFR_REQUIRE(sizes_ok(rows, V, F), "shaperender_forward: rows=%d V=%d F=%d (rows 1..4096, V and F 1..2^24)", rows, V, F);
     SGDFR_REQUIRE(S >= 1 && S <= kMaxSize, "shaperender_forward: size=%d (1..%d)", S, kMaxSize);
     SGDFR_REQUIRE((projected != nullptr) != (cam != nullptr), "shaperender_forward: exactly one of projected / cam");
     SGDFR_REQUIRE(!cam || vertices, "shaperender_forward: cam needs the world vertices");
-    const bool shade = shape != nullptr || det != nullptr;
-    if (shade) {
+    const bool shade = shape != nullptr || det != nullptr || tex != nullptr;
+    if (tex) {
+        SGDFR_REQUIRE(vertices && csr_offsets && csr_entries, "shaperender_texture: vertices and the vertex table are needed");
+    } else if (attr) {
+        SGDFR_REQUIRE(attr->values && attr->out && attr->D >= 1 && attr->D <= 3, "shaperender_attr: values [rows,V,D] with D 1..3 and out");
+    } else if (shade) {
         SGDFR_REQUIRE(vertices && csr_offsets && csr_entries && lights, "shaperender_forward: shading needs vertices, the vertex table and lights");
         SGDFR_REQUIRE(L >= 1 && L <= kMaxLights, "shaperender_forward: %d lights (1..%d)", L, kMaxLights);
         SGDFR_REQUIRE(light_rows == 1 || light_rows == rows, "shaperender_forward: lights for %d rows (1 or %d)", light_rows, rows);
@@ -395,20 +484,28 @@ static int forward(const float* vertices, const float* projected, const float* c
     hipStream_t st = as_stream(stream);
     project_kernel<<<dim3((V + 255) / 256, rows), 256, 0, st>>>(cam ? vertices : projected, cam, z_offset, V, ws.proj);
     if (check_launch("shaperender project_kernel")) return 1;
+    float* wn = normals ? normals : ws.wn;             // the textured render writes the world normals where the caller wants them
     if (shade) {
-        if (launch_normals(vertices, rows, V, faces, F, csr_offsets, csr_entries, 0, ws.wn, st)) return 1;
+        if (launch_normals(vertices, rows, V, faces, F, csr_offsets, csr_entries, 0, wn, st)) return 1;
         if (launch_normals(ws.proj, rows, V, faces, F, csr_offsets, csr_entries, 1, ws.tz, st)) return 1;
+        if (tnormals && launch_normals(ws.proj, rows, V, faces, F, csr_offsets, csr_entries, 0, tnormals, st)) return 1;
     }
     setup_kernel<<<dim3((F + 255) / 256, rows), 256, 0, st>>>(ws.proj, V, faces, F, S, ws.rec, ws.box);
     if (check_launch("shaperender setup_kernel")) return 1;
     RasterOut out{shape, alpha, pix_to_face, zbuf, bary};
     const int tiles = (S + kTile - 1) / kTile;
-    if (det)
-        raster_kernel<true><<<dim3(tiles, tiles, rows), kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L,
-                                                                        background, gan_range, out, *det);
+    const dim3 grid(tiles, tiles, rows);
+    if (tex)
+        raster_kernel<kTexture, TexIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, wn, ws.tz, lights, rows, 0, nullptr, 0, out, *tex);
+    else if (attr)
+        raster_kernel<kAttr, AttrIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, out,
+                                                             *attr);
+    else if (det)
+        raster_kernel<kDetail, DetailIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L, background,
+                                                                 gan_range, out, *det);
     else
-        raster_kernel<false><<<dim3(tiles, tiles, rows), kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L,
-                                                                         background, gan_range, out, DetailIO{});
+        raster_kernel<kShape, DetailIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L, background,
+                                                                gan_range, out, DetailIO{});
     return check_launch("shaperender raster_kernel");
 }
 
@@ -432,4 +529,32 @@ extern "C" int sgdfr_shaperender_detail_f32(const float* vertices, const float* 
     const DetailIO det{face_uv, uv_normals, Su, shape_detail, grid, detail_normal_images};
     return forward(vertices, projected, cam, z_offset, rows, V, faces, F, csr_offsets, csr_entries, S, lights, light_rows, L, background,
                    gan_range, shape, alpha, pix_to_face, zbuf, bary, &det, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgdfr_shaperender_texture_f32(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V,
+                                             const int* faces, int F, const int* csr_offsets, const int* csr_entries, int S,
+                                             const float* sh_lights, const float* sh_constants, const float* face_uv, const float* albedo,
+                                             int Su, float* images, float* albedo_images, float* alpha_images, float* pos_mask,
+                                             float* shading_images, float* grid, float* normal_images, float* normals,
+                                             float* transformed_normals, int* pix_to_face, float* zbuf, float* bary, void* workspace,
+                                             int64_t workspace_bytes, void* stream) {
+    SGDFR_REQUIRE(face_uv && sh_constants, "shaperender_texture: null face_uv or sh_constants");
+    SGDFR_REQUIRE(albedo || (!images && !albedo_images), "shaperender_texture: images and albedo_images need an albedo");
+    SGDFR_REQUIRE(Su >= 1 && Su <= kMaxSize, "shaperender_texture: uv_size=%d (1..%d)", Su, kMaxSize);
+    SGDFR_REQUIRE(images || albedo_images || alpha_images || pos_mask || shading_images || grid || normal_images || normals ||
+                      transformed_normals || pix_to_face || zbuf || bary,
+                  "shaperender_texture: no output");
+    TexIO tex{face_uv, albedo, Su, {}, images, albedo_images, alpha_images, pos_mask, shading_images, grid, normal_images};
+    for (int k = 0; k < 9; ++k) tex.sh[k] = sh_constants[k];
+    return forward(vertices, projected, cam, z_offset, rows, V, faces, F, csr_offsets, csr_entries, S, sh_lights, rows, 0, nullptr, 0, nullptr,
+                   nullptr, pix_to_face, zbuf, bary, nullptr, workspace, workspace_bytes, stream, &tex, normals, transformed_normals);
+}
+
+extern "C" int sgdfr_shaperender_attr_f32(const float* projected, float z_offset, int rows, int V, const int* faces, int F, int S,
+                                          const float* values, int D, float* out, int* pix_to_face, float* zbuf, float* bary, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+    SGDFR_REQUIRE(projected, "shaperender_attr: null projected");
+    const AttrIO attr{values, D, out};
+    return forward(nullptr, projected, nullptr, z_offset, rows, V, faces, F, nullptr, nullptr, S, nullptr, 0, 0, nullptr, 0, nullptr, nullptr,
+                   pix_to_face, zbuf, bary, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, &attr);
 }

@@ -16,8 +16,8 @@ construction; the HIP kernels run it in eval mode.  Its six BatchNorms are folde
 the Linear, the other five are nn.BatchNorm2d(C, 0.8), whose second argument is eps = 0.8 -- and each upsample + conv layer is one
 launch whose gather computes the bilinear value on the fly (no upsampled tensor exists).  `UvLayout` holds the UV side of a mesh and,
 per device, the UV table (pix_to_face, bary) that shape_render.rasterize gives for the UV vertices.  Forward only, no host
-synchronisation: everything runs on the current stream and captures into a graph.  Out of scope: the texture side (albedo sampling,
-add_SHlight, uv_texture, uv_texture_gt), visofp, render_depth / render_normal, and any backward.
+synchronisation: everything runs on the current stream and captures into a graph.  The texture side (albedo sampling, add_SHlight,
+uv_texture, uv_texture_gt), visofp, render_depth / render_normal and decode_deca as a whole are texture.py; any backward is out of scope.
 """
 import numpy as np
 import torch

@@ -252,6 +252,71 @@ def topology(flame):
     return cached[1]
 
 
+class LandmarkTable:
+    """Landmarks embedded in a triangle mesh, as FLAME's full_lmk_faces_idx / full_lmk_bary_coords are: faces [F,3], per landmark the
+    face it lies in [n] and its barycentric weights [n,3].  Resolved on the host to corner vertices; the device copies are made on
+    first use.  visofp takes one in place of a FLAME module, for any mesh."""
+
+    def __init__(self, faces, lmk_faces_idx, lmk_bary_coords, n_vertices):
+        faces = torch.as_tensor(faces).detach().cpu().long()
+        idx = torch.as_tensor(lmk_faces_idx).detach().cpu().long().reshape(-1)
+        bary = torch.as_tensor(lmk_bary_coords).detach().cpu().float().reshape(-1, 3)
+        if faces.ndim != 2 or faces.shape[1] != 3 or idx.numel() < 1 or bary.shape[0] != idx.numel():
+            raise RuntimeError('LandmarkTable: expected faces [F,3], face indices [n] and weights [n,3], got %s, %s, %s'
+                               % (tuple(faces.shape), tuple(idx.shape), tuple(bary.shape)))
+        if int(idx.min()) < 0 or int(idx.max()) >= faces.shape[0] or int(faces.min()) < 0 or int(faces.max()) >= n_vertices:
+            raise RuntimeError('LandmarkTable: a face or vertex index lies outside the mesh')
+        self.n, self.n_vertices = int(idx.numel()), int(n_vertices)
+        self.corners, self.bary = faces[idx].to(torch.int32).contiguous(), bary.contiguous()
+        self._device = {}
+
+    def tables(self, device):
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = (self.corners.to(device), self.bary.to(device))
+        return self._device[key]
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state['_device'] = {}
+        return state
+
+
+def landmark_table(flame):
+    """The LandmarkTable of a FLAME module's 68 full landmarks (seletec_3d68), rebuilt when one of its three buffers changes."""
+    ts = (flame.faces_tensor, flame.full_lmk_faces_idx, flame.full_lmk_bary_coords)
+    key = tuple((t.data_ptr(), t._version, str(t.device)) for t in ts)
+    cached = flame.__dict__.get('_lmk_table')
+    if cached is None or cached[0] != key:
+        cached = flame.__dict__['_lmk_table'] = (key, LandmarkTable(ts[0], ts[1], ts[2], int(flame.v_template.shape[0])))
+    return cached[1]
+
+
+VISOFP_Z = 0.1                                         # deca.py:147
+
+
+def visofp(flame, transformed_normals):
+    """DECA.visofp (deca.py:143-148): the normals of the projected vertices [B,V,3] gathered at the 68 landmarks of seletec_3d68,
+    1 where their z is below 0.1 -> [B,68,1].  flame: a FLAME module, or a LandmarkTable for another mesh.  Forward only."""
+    table = flame if isinstance(flame, LandmarkTable) else landmark_table(flame) if isinstance(flame, FLAME) else None
+    if table is None:
+        raise RuntimeError('visofp: expected a FLAME module or a LandmarkTable, got %s' % type(flame))
+    t = transformed_normals
+    if not torch.is_tensor(t):
+        raise RuntimeError('visofp: transformed_normals must be a tensor, got %s' % type(t))
+    N.require_device(t)
+    if t.ndim != 3 or t.shape[0] < 1 or tuple(t.shape[1:]) != (table.n_vertices, 3):
+        raise RuntimeError('visofp: expected transformed_normals of shape [B,%d,3], got %s' % (table.n_vertices, tuple(t.shape)))
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise RuntimeError('visofp: forward only (the result is a 0 / 1 mask); call it under torch.no_grad() or on a detached tensor')
+    t = N.f32c(t.detach())
+    corners, bary = table.tables(t.device)
+    vis = torch.empty((t.shape[0], table.n, 1), dtype=torch.float32, device=t.device)
+    N.call('sgdfr_flame_visofp_f32', N.ptr(t), t.shape[0], table.n_vertices, N.ptr(corners), N.ptr(bary), table.n, VISOFP_Z, N.ptr(vis), None,
+           N.stream())
+    return vis
+
+
 def shape_images(flame, codedict, size=224, images=None, gan_range=False):
     """The `shape_images` of DECA.decode_deca (deca.py:175-187): FLAME forward, the camera projection and SRenderY.render_shape ->
     [B,3,size,size], the grey lit mesh over `images` (None: black).  codedict is what deca.encode / train_step.shape_params return

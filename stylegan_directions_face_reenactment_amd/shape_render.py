@@ -8,6 +8,9 @@ rasterize_meshes at the fixed settings of renderer.py:40-47).  Forward only: the
     normals = vertex_normals(vertices, topo)                            # util.vertex_normals
     pix_to_face, zbuf, bary = rasterize(projected, topo, 256)           # rasterize_meshes: one face per pixel, blur_radius 0
 
+    ops = render_texture(vertices, topo, layout, albedo, lights=sh, cam=cam, want=('images', 'grid', 'normals'))      # SRenderY.forward
+    normal_images = render_normal(projected, normals, topo, 224)        # SRenderY.render_normal, render_depth likewise
+
 Five launches (project, normals of the world and of the projected vertices, face setup, raster + shade), no atomics and a fixed face
 order: results are bit-identical from call to call; no host synchronisation, so a call captures into a graph.  The rasteriser's rules
 are restated from pytorch3d's documented behaviour (include/sgdfr.h); on equal depth the lower face index wins.
@@ -22,6 +25,13 @@ DEFAULT_LIGHTS = tuple((x, y, z, 1.7, 1.7, 1.7) for x, y, z in ((-1, 1, 1), (1, 
 Z_OFFSET = 10.0                                     # renderer.py:255
 _WANT = ('shape', 'alpha', 'pix_to_face', 'zbuf', 'bary')
 _WANT_DETAIL = ('shape_detail', 'grid', 'detail_normal_images')      # with layout and detail_normals only
+_WANT_TEXTURE = ('images', 'albedo_images', 'alpha_images', 'pos_mask', 'shading_images', 'grid', 'normal_images', 'normals',
+                 'transformed_normals', 'pix_to_face', 'zbuf', 'bary')      # render_texture
+# renderer.py:114-119, evaluated in double and rounded to float once
+_PI = np.pi
+SH_CONSTANTS = tuple(float(np.float32(c)) for c in (
+    [1 / np.sqrt(4 * _PI)] + [((2 * _PI) / 3) * np.sqrt(3 / (4 * _PI))] * 3 + [(_PI / 4) * 3 * np.sqrt(5 / (12 * _PI))] * 3
+    + [(_PI / 4) * (3 / 2) * np.sqrt(5 / (12 * _PI)), (_PI / 4) * (1 / 2) * np.sqrt(5 / (4 * _PI))]))
 
 
 class MeshTopology:
@@ -232,3 +242,127 @@ def render_shape(vertices, topo, cam=None, projected=None, size=224, images=None
            N.ptr(out['shape']), N.ptr(out.get('alpha')), N.ptr(out.get('pix_to_face')), N.ptr(out.get('zbuf')), N.ptr(out.get('bary')),
            N.ptr(ws), nbytes, N.stream())
     return out
+
+
+def _forward_only(who, *tensors):
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors):
+        raise RuntimeError('%s: forward only (no gradient reaches its inputs); call it under torch.no_grad() or on detached tensors' % who)
+
+
+def _check_map(who, name, t, shape):
+    if not torch.is_tensor(t):
+        raise RuntimeError('%s: %s must be a tensor, got %s' % (who, name, type(t)))
+    N.require_device(t)
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError('%s: expected %s of shape [%s], got %s' % (who, name, ','.join(map(str, shape)), tuple(t.shape)))
+    return N.f32c(t.detach())
+
+
+def sh_constants():
+    """The nine factors as the host array the texture entries take."""
+    import ctypes
+    return (ctypes.c_float * 9)(*SH_CONSTANTS)
+
+
+def render_texture(vertices, topo, layout, albedo, lights=None, cam=None, projected=None, size=224, want=('images',)):
+    """SRenderY.forward (renderer.py:121-191) from one rasterisation: world vertices [B,V,3], exactly one of cam [B,3] and projected
+    [B,V,3] (as render_shape takes them), layout (a detail.UvLayout of this mesh), albedo [B,3,Su,Su] at the layout's uv_size (None
+    where neither 'images' nor 'albedo_images' is wanted) and lights [B,9,3] (spherical harmonics; None: no shading) -> a dict of what `want` names:
+
+      'images' [B,3,S,S] = albedo_images * shading_images * alpha ('albedo_images' with lights=None);
+      'albedo_images' = grid_sample(albedo, grid) * alpha;  'alpha_images' [B,1,S,S]: the coverage, with no front-facing mask;
+      'pos_mask' [B,1,S,S]: interpolated transformed-normal z < -0.05;  'normal_images' = the interpolated world normal * alpha;
+      'shading_images' = add_SHlight of the interpolated world normal, not renormalised and NOT masked by alpha, as in the reference: an
+        uncovered pixel has normal 0 and the value c0 L0 - c8 L8 (0 everywhere with lights=None);
+      'grid' [B,S,S,2], bit for bit render_shape's;  'normals', 'transformed_normals' [B,V,3];  'pix_to_face', 'zbuf', 'bary'.
+
+    Point and directional lights ([B,L,6] through SRenderY.forward) are not built.  No argument is modified."""
+    who = 'render_texture'
+    _check_topology(who, topo)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _WANT_TEXTURE for w in want):
+        raise RuntimeError('%s: want must name at least one of %s, got %r' % (who, _WANT_TEXTURE, want))
+    if (cam is None) == (projected is None):
+        raise RuntimeError('%s: exactly one of cam and projected must be given' % who)
+    from .detail import UvLayout
+    if not isinstance(layout, UvLayout):
+        raise RuntimeError('%s: layout must be a detail.UvLayout, got %s' % (who, type(layout)))
+    if layout.n_faces != topo.n_faces or layout.n_vertices != topo.n_vertices:
+        raise RuntimeError('%s: the layout is for a mesh of %d vertices and %d faces, topo has %d and %d'
+                           % (who, layout.n_vertices, layout.n_faces, topo.n_vertices, topo.n_faces))
+    _forward_only(who, vertices, albedo, lights, cam, projected)
+    v = _check_vertices(who, 'vertices', vertices, topo)
+    _check_size(who, size)
+    B, dev, Su = v.shape[0], v.device, layout.uv_size
+    if cam is not None:
+        cam = _check_map(who, 'cam', cam, (B, 3))
+    else:
+        projected = _check_vertices(who, 'projected', projected, topo, B)
+    if albedo is None:
+        if 'images' in want or 'albedo_images' in want:
+            raise RuntimeError("%s: 'images' and 'albedo_images' need an albedo" % who)
+    else:
+        albedo = _check_map(who, 'albedo', albedo, (B, 3, Su, Su))
+    if lights is not None:
+        if torch.is_tensor(lights) and lights.ndim == 3 and lights.shape[2] == 6:
+            raise RuntimeError('%s: point and directional lights [B,L,6] have no HIP kernel here; pass spherical-harmonic lights [B,9,3]' % who)
+        lights = _check_map(who, 'lights', lights, (B, 9, 3))
+    if any(t is not None and t.device != dev for t in (cam, projected, albedo, lights)):
+        raise RuntimeError('%s: all tensors must live on the vertices\' device %s' % (who, dev))
+    faces, offsets, entries = topo.tables(dev)
+    V, S = topo.n_vertices, size
+    shapes = {'images': (B, 3, S, S), 'albedo_images': (B, 3, S, S), 'alpha_images': (B, 1, S, S), 'pos_mask': (B, 1, S, S),
+              'shading_images': (B, 3, S, S), 'grid': (B, S, S, 2), 'normal_images': (B, 3, S, S), 'normals': (B, V, 3),
+              'transformed_normals': (B, V, 3), 'pix_to_face': (B, S, S), 'zbuf': (B, S, S), 'bary': (B, S, S, 3)}
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == 'pix_to_face' else torch.float32, device=dev) for k in _WANT_TEXTURE if k in want}
+    ws, nbytes = _workspace(B, topo, dev)
+    face_uv = layout.tables(dev)[5]
+    N.call('sgdfr_shaperender_texture_f32', N.ptr(v), N.ptr(projected), N.ptr(cam), Z_OFFSET, B, V, N.ptr(faces), topo.n_faces, N.ptr(offsets),
+           N.ptr(entries), S, N.ptr(lights), sh_constants(), N.ptr(face_uv), N.ptr(albedo), Su, *[N.ptr(out.get(k)) for k in _WANT_TEXTURE],
+           N.ptr(ws), nbytes, N.stream())
+    return out
+
+
+def _render_attr(who, projected, values, topo, size, z_offset):
+    _check_topology(who, topo)
+    _forward_only(who, projected, values)
+    p = _check_vertices(who, 'projected', projected, topo)
+    _check_size(who, size)
+    if not torch.is_tensor(values):
+        raise RuntimeError('%s: the per-vertex values must be a tensor, got %s' % (who, type(values)))
+    N.require_device(values)
+    B, V = p.shape[0], topo.n_vertices
+    if values.ndim != 3 or tuple(values.shape[:2]) != (B, V) or not 1 <= values.shape[2] <= 3:
+        raise RuntimeError('%s: expected per-vertex values of shape [%d,%d,1..3], got %s' % (who, B, V, tuple(values.shape)))
+    if values.device != p.device:
+        raise RuntimeError('%s: all tensors must live on one device' % who)
+    a = N.f32c(values.detach())
+    D = a.shape[2]
+    faces, _, _ = topo.tables(p.device)
+    out = torch.empty((B, D, size, size), dtype=torch.float32, device=p.device)
+    ws, nbytes = _workspace(B, topo, p.device)
+    N.call('sgdfr_shaperender_attr_f32', N.ptr(p), float(z_offset), B, V, N.ptr(faces), topo.n_faces, size, N.ptr(a), D, N.ptr(out), None, None,
+           None, N.ptr(ws), nbytes, N.stream())
+    return out
+
+
+def render_normal(projected, normals, topo, size=224, z_offset=0.0):
+    """SRenderY.render_normal (renderer.py:316-329): per-vertex values [B,V,3] interpolated over the rasterisation of projected
+    [B,V,3] -> [B,3,S,S], 0 where no face covers.  The reference rasterises what it is given -- by the time DECA calls it, 10 has been
+    added to z in place -- so z_offset is 0 here; pass z_offset=10 for vertices that still hold DECA's projected z."""
+    return _render_attr('render_normal', projected, normals, topo, size, z_offset)
+
+
+def render_depth(projected, topo, size=224):
+    """SRenderY.render_depth (renderer.py:295-314): [B,1,S,S], 1 for the nearest vertex of the whole batch, 0 for the farthest and
+    where no face covers.  The minimum and maximum over the batch are torch reductions on the device in front of the launch (no host
+    synchronisation); the vertices are rasterised at z - min(z) + 10, and the caller's tensor is not modified."""
+    who = 'render_depth'
+    _check_topology(who, topo)
+    _forward_only(who, projected)
+    p = _check_vertices(who, 'projected', projected, topo)
+    z = p[:, :, 2:] - p[:, :, 2].min()
+    d = -z
+    d = d - d.min()
+    d = d / d.max()
+    return _render_attr(who, torch.cat([p[:, :, :2], z], 2), d, topo, size, Z_OFFSET)
