@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "conv_tile.h"
+#include "mesh_sample.h"
 
 #pragma clang fp contract(off)
 
@@ -265,17 +266,8 @@ __global__ __launch_bounds__(256) void world2uv_kernel(const float* __restrict__
                                                        float* __restrict__ out) {
     const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x, plane = S * S;
     if (t >= plane) return;
-    float r[3] = {0.f, 0.f, 0.f};
-    const unsigned f = (unsigned)pix_to_face[t];
-    if (f < (unsigned)F) {
-        const unsigned i0 = (unsigned)faces[f * 3], i1 = (unsigned)faces[f * 3 + 1], i2 = (unsigned)faces[f * 3 + 2];
-        if (i0 < (unsigned)V && i1 < (unsigned)V && i2 < (unsigned)V) {
-            const float* p = values + (size_t)b * V * 3;
-            const float w0 = bary[t * 3], w1 = bary[t * 3 + 1], w2 = bary[t * 3 + 2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) r[c] = w0 * p[i0 * 3 + c] + w1 * p[i1 * 3 + c] + w2 * p[i2 * 3 + c];
-        }
-    }
+    float r[3];
+    bary_gather3(values + (size_t)b * V * 3, V, faces, F, pix_to_face, bary, t, r);
     float* o = out + (size_t)b * 3 * plane + t;
     o[0] = r[0], o[plane] = r[1], o[2 * (size_t)plane] = r[2];
 }
@@ -305,19 +297,12 @@ __global__ __launch_bounds__(kTile * kTile) void uvnormals_kernel(const float* _
         float P[3] = {0.f, 0.f, 0.f};
         if (y >= 0 && y < S && x >= 0 && x < S) {
             const int tex = y * S + x;
-            const unsigned f = (unsigned)pix_to_face[tex];
-            if (f < (unsigned)F) {
-                const unsigned i0 = (unsigned)faces[f * 3], i1 = (unsigned)faces[f * 3 + 1], i2 = (unsigned)faces[f * 3 + 2];
-                if (i0 < (unsigned)V && i1 < (unsigned)V && i2 < (unsigned)V) {
-                    const float w0 = bary[tex * 3], w1 = bary[tex * 3 + 1], w2 = bary[tex * 3 + 2];
-                    const float z = uv_z[(size_t)b * plane + tex] * mask[tex], d = fixed_dis[tex];
+            float v[3], n[3];
+            // the second gather is made only under a covered texel, so an uncovered one stays exactly 0 whatever z and d hold
+            if (bary_gather3(pv, V, faces, F, pix_to_face, bary, tex, v) && bary_gather3(pn, V, faces, F, pix_to_face, bary, tex, n)) {
+                const float z = uv_z[(size_t)b * plane + tex] * mask[tex], d = fixed_dis[tex];
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float v = w0 * pv[i0 * 3 + c] + w1 * pv[i1 * 3 + c] + w2 * pv[i2 * 3 + c];
-                        const float n = w0 * pn[i0 * 3 + c] + w1 * pn[i1 * 3 + c] + w2 * pn[i2 * 3 + c];
-                        P[c] = (v + z * n) + d * n;
-                    }
-                }
+                for (int c = 0; c < 3; ++c) P[c] = (v[c] + z * n[c]) + d * n[c];
             }
             if (dense && cy >= 1 && cy <= kTile && cx >= 1 && cx <= kTile) {
                 float* o = dense + ((size_t)b * plane + tex) * 3;

@@ -8,27 +8,24 @@
 //                                       empty box (x0 > x1) marks a face that is skipped or wholly outside
 //   raster     1 block / 16 x 16 tile   walks the faces in chunks of 256: one bounding-box test per thread, the hits compacted in face
 //                                       order (wave ballot, popcount prefix, cross-wave offset in LDS), their records copied to LDS,
-//                                       then every thread tests its own pixel against the compacted list; the epilogue interpolates,
+//                                       then every thread tests its own pixel against the compacted list; a shader interpolates,
 //                                       lights and blends the winner, so no attribute image exists
 // No global bins, no atomics, a fixed face order: the result does not depend on scheduling.  All 256 threads read the same LDS record
 // at the same time (three ds_read_b128 of one address: a broadcast, no bank conflict).
 //
-// sgdfr_shaperender_detail_f32 is the same five launches with raster_kernel<true>: one rasterisation serves the smooth panel and the
-// detail panel, whose shading normal is the UV normal map sampled at the pixel's interpolated UV coordinate (grid_sample rules).  The
-// reference renders three times and adds z_offset = 10 to the caller's projected vertices in place each time (renderer.py:255); the
-// projection is orthographic, so a constant shift of z changes no coverage, no barycentric and no depth order, and every |z| < 10
-// stays in front of the z >= 0 cut whether 10, 20 or 30 was added: z_offset stays 10 here and no argument is modified.
-//
-// sgdfr_shaperender_texture_f32 is the third instance, raster_kernel<kTexture>: SRenderY.forward (renderer.py:121-191), the albedo map
-// sampled at the pixel's UV coordinate, add_SHlight on the interpolated world normal, the coverage and the z < -0.05 mask of the
-// projected normals.  sgdfr_shaperender_attr_f32 is the fourth, raster_kernel<kAttr>: D <= 3 per-vertex values interpolated, 0 where no
-// face covers (render_normal, render_depth; no normals are computed: three launches).
+// The raster kernel is one walk and four shaders: raster_kernel<Shader> = the shader's prologue (lights into LDS), cover() (the walk
+// above, which knows nothing of shading and returns the pixel's Hit), write_raster (pix_to_face, zbuf, bary) and the shader on the
+// Hit.  A shader (ShapeShader, DetailShader, TextureShader, AttrShader below) is a struct of its own inputs and outputs, passed by
+// value as a kernel argument; what more than one needs (corners, mix3, normal_at, face_uv_at, directional; grid_sample3 and sh_light
+// of mesh_sample.h) is written once.  The host side is as it was: forward() with the entries' common checks and launches; z_offset
+// stays 10 however often the reference adds it in place (orthographic: a shift of |z| < 10 changes nothing).
 //
 // Floating-point contraction is OFF for the whole file: coverage is a sign test on differences of products, and the tests compare
 // it with a restatement that does not fuse.
 #include <math.h>
 
 #include "common.h"
+#include "mesh_sample.h"
 
 #pragma clang fp contract(off)
 
@@ -42,6 +39,7 @@ constexpr int kMaxSize = 4096;               // the bounding box is stored in 16
 constexpr float kAreaEps = 1e-8f;            // pytorch3d's kEpsilon: |area| <= eps is skipped, the barycentrics divide by area + eps
 constexpr float kAlbedo = 180.0f / 255.0f;   // renderer.py:110
 constexpr float kFrontZ = 0.15f;             // renderer.py:276
+constexpr float kPosZ = -0.05f;              // renderer.py:159
 
 struct FaceRec {                             // 48 bytes: three 16-byte LDS reads
     float ax, ay, bx, by;
@@ -177,107 +175,19 @@ __global__ __launch_bounds__(256) void setup_kernel(const float* __restrict__ pr
     box[at] = bb;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- raster + shade
+// ---------------------------------------------------------------------------------------------------------------- raster: the cover
 struct RasterOut {
-    float* shape;            // [B,3,S,S] or NULL
-    float* alpha;            // [B,1,S,S] or NULL
     int* pix_to_face;        // [B,S,S] or NULL
     float* zbuf;             // [B,S,S] or NULL
     float* bary;             // [B,S,S,3] or NULL
 };
+struct Hit { int face; float z, w0, w1, w2; };       // the nearest face over one pixel centre and its barycentrics; face < 0: none
+// what forward() tells every shader of the mesh and the image; wn, tz [B,V,3], [B,V]: only where the entry computes the normals
+struct Mesh { const int* faces; int V, S; const float *wn, *tz; };
 
-// the detail panel's inputs and outputs (sgdfr_shaperender_detail_f32); unused by raster_kernel<false>
-struct DetailIO {
-    const float* face_uv;    // [F,3,2]
-    const float* uv_normals; // [B,3,Su,Su]
-    int Su;
-    float* shape_detail;     // [B,3,S,S] or NULL
-    float* grid;             // [B,S,S,2] or NULL
-    float* normal_images;    // [B,3,S,S] or NULL
-};
-
-// the textured render's inputs and outputs (sgdfr_shaperender_texture_f32); every output may be NULL
-struct TexIO {
-    const float* face_uv;    // [F,3,2]
-    const float* albedo;     // [B,3,Su,Su]
-    int Su;
-    float sh[9];             // renderer.py:114-119, rounded to float once on the host
-    float* images;           // [B,3,S,S]
-    float* albedo_images;    // [B,3,S,S]
-    float* alpha;            // [B,1,S,S]
-    float* pos_mask;         // [B,1,S,S]
-    float* shading;          // [B,3,S,S]
-    float* grid;             // [B,S,S,2]
-    float* normal_images;    // [B,3,S,S]
-};
-
-// the attribute mode (sgdfr_shaperender_attr_f32)
-struct AttrIO {
-    const float* values;     // [B,V,D]
-    int D;                   // 1..3
-    float* out;              // [B,D,S,S]
-};
-
-constexpr int kShape = 0, kDetail = 1, kTexture = 2, kAttr = 3;      // raster_kernel's modes
-constexpr float kPosZ = -0.05f;              // renderer.py:159
-
-// F.grid_sample(bilinear, zeros, align_corners=False) of one [3,Su,Su] map at g: a neighbour outside the map adds nothing
-__device__ __forceinline__ void sample_uv(const float* __restrict__ map, int Su, float gx, float gy, float (&r)[3]) {
-    const float ix = ((gx + 1.0f) * (float)Su - 1.0f) * 0.5f, iy = ((gy + 1.0f) * (float)Su - 1.0f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    const float ax = ix - fx, ay = iy - fy, bx = (fx + 1.0f) - ix, by = (fy + 1.0f) - iy;
-    r[0] = r[1] = r[2] = 0.f;
-    // a coordinate that is not finite or far outside fails every test below (the casts are then never made)
-    if (!(fx >= -1.0f && fx < (float)Su && fy >= -1.0f && fy < (float)Su)) return;
-    const int x0 = (int)fx, y0 = (int)fy;
-    const size_t plane = (size_t)Su * Su;
-    const float w[4] = {bx * by, ax * by, bx * ay, ax * ay};      // nw, ne, sw, se
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x = x0 + (k & 1), y = y0 + (k >> 1);
-        if (x < 0 || x >= Su || y < 0 || y >= Su) continue;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) r[c] += map[c * plane + (size_t)y * Su + x] * w[k];
-    }
-}
-
-// SRenderY.add_SHlight at one normal: sum_k coeff[k][c] (basis_k(n) constant_k), k ascending; coeff [9][3]
-__device__ __forceinline__ void sh_light(const float (&c)[9], const float* coeff, float nx, float ny, float nz, float (&r)[3]) {
-    const float basis[9] = {1.0f, nx, ny, nz, nx * ny, nx * nz, ny * nz, nx * nx - ny * ny, 3.0f * (nz * nz) - 1.0f};
-    r[0] = r[1] = r[2] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const float sh = basis[k] * c[k];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) r[ch] += coeff[k * 3 + ch] * sh;
-    }
-}
-
-template <int MODE, typename IO>
-__global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restrict__ rec, const ushort4* __restrict__ box, int F, int S, int V,
-                                                        const int* __restrict__ faces, const float* __restrict__ wn,
-                                                        const float* __restrict__ tz, const float* __restrict__ lights, int light_rows, int L,
-                                                        const float* __restrict__ background, int gan_range, RasterOut out, IO det) {
-    constexpr bool DETAIL = MODE == kDetail;
-    __shared__ float4 s_rec[kChunk][3];
-    __shared__ float s_light[kMaxLights][6];
-    __shared__ int s_wave[kChunk / kWave];
-    const int t = threadIdx.x, b = blockIdx.z;
-    const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
-    const int j = tx0 + (t & (kTile - 1)), i = ty0 + t / kTile;
-    const bool live = j < S && i < S;
-    const float px = __fdiv_rn((float)(2 * j + 1), (float)S) - 1.0f, py = __fdiv_rn((float)(2 * i + 1), (float)S) - 1.0f;
-    if constexpr (MODE == kTexture) {
-        if (lights && t < 27) (&s_light[0][0])[t] = lights[(size_t)b * 27 + t];       // this image's SH coefficients [9][3]
-    } else if ((DETAIL || (MODE == kShape && out.shape)) && t < L) {
-        // F.normalize(direction, eps=1e-12) and the intensities of this image's light t
-        const float* l = lights + ((size_t)(light_rows == 1 ? 0 : b) * L + t) * 6;
-        const float n = fmaxf(sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]), 1e-12f);
-        s_light[t][0] = __fdiv_rn(l[0], n), s_light[t][1] = __fdiv_rn(l[1], n), s_light[t][2] = __fdiv_rn(l[2], n);
-        s_light[t][3] = l[3], s_light[t][4] = l[4], s_light[t][5] = l[5];
-    }
-    const FaceRec* rec_b = rec + (size_t)b * F;
-    const ushort4* box_b = box + (size_t)b * F;
+// One tile's walk over the faces of its image in chunks of kChunk; p = the centre of this thread's pixel, live = it lies in the image.
+__device__ __forceinline__ Hit cover(const FaceRec* __restrict__ rec_b, const ushort4* __restrict__ box_b, int F, int t, int tx0, int ty0,
+                                     bool live, float px, float py, float4 (&s_rec)[kChunk][3], int (&s_wave)[kChunk / kWave]) {
     const int lane = t & (kWave - 1), wave = t / kWave;
     const int tx1 = tx0 + kTile - 1, ty1 = ty0 + kTile - 1;
     float best_z = INFINITY, w0 = 0.f, w1 = 0.f, w2 = 0.f;
@@ -326,109 +236,191 @@ __global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restric
         }
         // the barrier at the top of the next chunk keeps s_rec until every thread is through this loop
     }
-    if (!live) return;
-    const size_t pix = ((size_t)b * S + i) * S + j;
-    const bool covered = best >= 0;
-    if (out.pix_to_face) out.pix_to_face[pix] = best;
-    if (out.zbuf) out.zbuf[pix] = covered ? best_z : -1.0f;
+    return Hit{best, best_z, w0, w1, w2};
+}
+
+__device__ __forceinline__ void write_raster(const RasterOut& out, size_t pix, const Hit& h) {
+    const bool covered = h.face >= 0;
+    if (out.pix_to_face) out.pix_to_face[pix] = h.face;
+    if (out.zbuf) out.zbuf[pix] = covered ? h.z : -1.0f;
     if (out.bary) {
-        out.bary[pix * 3] = covered ? w0 : -1.0f;
-        out.bary[pix * 3 + 1] = covered ? w1 : -1.0f;
-        out.bary[pix * 3 + 2] = covered ? w2 : -1.0f;
+        out.bary[pix * 3] = covered ? h.w0 : -1.0f;
+        out.bary[pix * 3 + 1] = covered ? h.w1 : -1.0f;
+        out.bary[pix * 3 + 2] = covered ? h.w2 : -1.0f;
     }
-    if constexpr (MODE == kAttr) {
-        float r[3] = {0.f, 0.f, 0.f};
-        if (covered) {
-            const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];
-            const float* a = det.values + (size_t)b * V * det.D;
-            for (int c = 0; c < det.D; ++c) r[c] = w0 * a[i0 * det.D + c] + w1 * a[i1 * det.D + c] + w2 * a[i2 * det.D + c];
-        }
-        for (int c = 0; c < det.D; ++c) det.out[((size_t)b * det.D + c) * S * S + (size_t)i * S + j] = r[c];
-    } else if constexpr (MODE == kTexture) {
-        // SRenderY.forward: an uncovered pixel has every attribute 0, so its shading is add_SHlight(0) and everything else 0
-        float n[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f}, sh[3] = {0.f, 0.f, 0.f}, tzp = 0.f, gx = 0.f, gy = 0.f;
-        const float a = covered ? 1.0f : 0.0f;
-        if (covered) {
-            const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];
-            const float* nw = wn + (size_t)b * V * 3;
-            const float* z = tz + (size_t)b * V;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- what the shaders share
+// the three vertices k of a face that won a pixel (in range: setup skipped the others), and component c of a per-vertex table of
+// `stride` floats a vertex interpolated over them: w0 a + w1 b + w2 c in this association
+__device__ __forceinline__ const int* corners(const int* __restrict__ faces, int face) { return faces + face * 3; }
+__device__ __forceinline__ float mix3(const Hit& h, const float* __restrict__ a, const int* __restrict__ k, int stride, int c) {
+    return h.w0 * a[k[0] * stride + c] + h.w1 * a[k[1] * stride + c] + h.w2 * a[k[2] * stride + c];
+}
+
+// the interpolated world normal under a hit (not renormalised); returns the interpolated z of the projected normals
+__device__ __forceinline__ float normal_at(const Mesh& m, int b, const Hit& h, float (&n)[3]) {
+    const int* k = corners(m.faces, h.face);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) n[c] = w0 * nw[i0 * 3 + c] + w1 * nw[i1 * 3 + c] + w2 * nw[i2 * 3 + c];
-            tzp = w0 * z[i0] + w1 * z[i1] + w2 * z[i2];
-            const float* uv = det.face_uv + (size_t)best * 6;
-            gx = w0 * uv[0] + w1 * uv[2] + w2 * uv[4];
-            gy = w0 * uv[1] + w1 * uv[3] + w2 * uv[5];
-            if (det.images || det.albedo_images) sample_uv(det.albedo + (size_t)b * 3 * det.Su * det.Su, det.Su, gx, gy, al);
+    for (int c = 0; c < 3; ++c) n[c] = mix3(h, m.wn + (size_t)b * m.V * 3, k, 3, c);
+    return mix3(h, m.tz + (size_t)b * m.V, k, 1, 0);
+}
+
+// the pixel's UV coordinate (ops['grid']); face_uv [F,3,2]
+__device__ __forceinline__ void face_uv_at(const float* __restrict__ face_uv, const Hit& h, float& gx, float& gy) {
+    const float* uv = face_uv + (size_t)h.face * 6;
+    gx = h.w0 * uv[0] + h.w1 * uv[2] + h.w2 * uv[4], gy = h.w0 * uv[1] + h.w1 * uv[3] + h.w2 * uv[5];
+}
+
+// sum over the staged lights [L][6] = unit direction, intensity: clamp(n . direction, 0, 1) intensity (renderer.py:226-235)
+__device__ __forceinline__ void directional(const float* s_light, int L, const float (&n)[3], float (&shade)[3]) {
+    shade[0] = shade[1] = shade[2] = 0.f;
+    for (int l = 0; l < L; ++l, s_light += 6) {
+        const float d = fminf(fmaxf(n[0] * s_light[0] + n[1] * s_light[1] + n[2] * s_light[2], 0.0f), 1.0f);
+        shade[0] += d * s_light[3], shade[1] += d * s_light[4], shade[2] += d * s_light[5];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the four shaders
+// A shader has kLightFloats (the LDS it stages into), prologue(t, b, s_light) for thread t of a block of image b before the cover and
+// operator()(mesh, b, pix, hit, s_light) for one live pixel after it: pix = (b S + i) S + j, [B,C,S,S] at pix + ((C - 1) b + c) S S.
+struct DetailIO {            // what the detail panel adds to the grey one (sgdfr_shaperender_detail_f32)
+    const float* face_uv;    // [F,3,2]
+    const float* uv_normals; // [B,3,Su,Su]
+    int Su;
+    float *shape_detail, *normal_images, *grid;      // [B,3,S,S], [B,3,S,S], [B,S,S,2] or NULL
+};
+struct ShapeShader {         // sgdfr_shaperender_forward_f32 (SRenderY.render_shape); shape NULL: the cover alone (rasterize)
+    const float* lights;     // [light_rows,L,6] direction, intensity
+    int light_rows, L;
+    const float* background; // [B,3,S,S] or NULL
+    int gan_range;
+    float *shape, *alpha;    // [B,3,S,S], [B,1,S,S] or NULL
+    static constexpr int kLightFloats = kMaxLights * 6;
+
+    // F.normalize(direction, eps=1e-12) and the intensities of this image's light t (forward() sets L = 0 where nothing is lit)
+    __device__ __forceinline__ void prologue(int t, int b, float* s_light) const {
+        if (t >= L) return;
+        const float* l = lights + ((size_t)(light_rows == 1 ? 0 : b) * L + t) * 6;
+        const float n = fmaxf(sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]), 1e-12f);
+        float* s = s_light + t * 6;
+        s[0] = __fdiv_rn(l[0], n), s[1] = __fdiv_rn(l[1], n), s[2] = __fdiv_rn(l[2], n), s[3] = l[3], s[4] = l[4], s[5] = l[5];
+    }
+    // albedo . mean shading . alpha over the background (renderer.py:283-291)
+    __device__ __forceinline__ float blend(float shade, float albedo, float a, float bg) const {
+        const float v = albedo * __fdiv_rn(shade, (float)L) * a + bg * (1.0f - a);
+        return gan_range ? fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f : v;
+    }
+    // One live pixel of the grey panel and, with d, of the detail panel, which shares its albedo, alpha and background and takes its
+    // shading normal from the UV normal map at the pixel's UV coordinate (ops['grid']).  d is a constant of the instance: NULL folds away.
+    __device__ __forceinline__ void pixel(const Mesh& m, int b, size_t pix, const Hit& h, const float* s_light, const DetailIO* d) const {
+        float n[3], shade[3] = {0.f, 0.f, 0.f}, albedo = 0.f, a = 0.f, dn[3] = {0.f, 0.f, 0.f}, dshade[3] = {0.f, 0.f, 0.f}, gx = 0.f, gy = 0.f;
+        if (h.face >= 0) {
+            albedo = (h.w0 + h.w1 + h.w2) * kAlbedo;
+            a = normal_at(m, b, h, n) < kFrontZ ? 1.0f : 0.0f;       // renderer.py:272-277
+            directional(s_light, L, n, shade);
+            if (d) {
+                face_uv_at(d->face_uv, h, gx, gy);
+                grid_sample3(d->uv_normals + (size_t)b * 3 * d->Su * d->Su, d->Su, d->Su, gx, gy, dn);
+                directional(s_light, L, dn, dshade);
+            }
         }
-        if (lights) sh_light(det.sh, &s_light[0][0], n[0], n[1], n[2], sh);
-        if (det.grid) det.grid[pix * 2] = gx, det.grid[pix * 2 + 1] = gy;
-        if (det.alpha) det.alpha[pix] = a;
-        if (det.pos_mask) det.pos_mask[pix] = tzp < kPosZ ? 1.0f : 0.0f;
-        const size_t plane = (size_t)S * S;
-        const size_t o = (size_t)b * 3 * plane + (size_t)i * S + j;
+        if (d && d->grid) d->grid[pix * 2] = gx, d->grid[pix * 2 + 1] = gy;
+        if (alpha) alpha[pix] = a;
+        const size_t plane = (size_t)m.S * m.S, o = pix + 2 * b * plane;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if (det.images) det.images[o + c * plane] = (lights ? al[c] * sh[c] : al[c]) * a;
-            if (det.albedo_images) det.albedo_images[o + c * plane] = al[c] * a;
-            if (det.shading) det.shading[o + c * plane] = sh[c];
-            if (det.normal_images) det.normal_images[o + c * plane] = n[c] * a;
-        }
-    } else {
-        if (!DETAIL && !out.shape) return;
-        float shade[3] = {0.f, 0.f, 0.f}, albedo = 0.f, a = 0.f;
-        float dshade[3] = {0.f, 0.f, 0.f}, dn[3] = {0.f, 0.f, 0.f}, gx = 0.f, gy = 0.f;
-        if (covered) {
-            const int i0 = faces[best * 3], i1 = faces[best * 3 + 1], i2 = faces[best * 3 + 2];      // in range: setup skipped the others
-            const float* n = wn + (size_t)b * V * 3;
-            const float* z = tz + (size_t)b * V;
-            const float nx = w0 * n[i0 * 3] + w1 * n[i1 * 3] + w2 * n[i2 * 3];
-            const float ny = w0 * n[i0 * 3 + 1] + w1 * n[i1 * 3 + 1] + w2 * n[i2 * 3 + 1];
-            const float nz = w0 * n[i0 * 3 + 2] + w1 * n[i1 * 3 + 2] + w2 * n[i2 * 3 + 2];
-            const float tzp = w0 * z[i0] + w1 * z[i1] + w2 * z[i2];
-            albedo = (w0 + w1 + w2) * kAlbedo;
-            for (int l = 0; l < L; ++l) {
-                const float d = fminf(fmaxf(nx * s_light[l][0] + ny * s_light[l][1] + nz * s_light[l][2], 0.0f), 1.0f);
-                shade[0] += d * s_light[l][3], shade[1] += d * s_light[l][4], shade[2] += d * s_light[l][5];
-            }
-            a = tzp < kFrontZ ? 1.0f : 0.0f;
-            if constexpr (DETAIL) {
-                // ops['grid'] and the UV normal map sampled there: the detail panel's shading normal (covered = 1 here)
-                const float* uv = det.face_uv + (size_t)best * 6;
-                gx = w0 * uv[0] + w1 * uv[2] + w2 * uv[4];
-                gy = w0 * uv[1] + w1 * uv[3] + w2 * uv[5];
-                sample_uv(det.uv_normals + (size_t)b * 3 * det.Su * det.Su, det.Su, gx, gy, dn);
-                for (int l = 0; l < L; ++l) {
-                    const float d = fminf(fmaxf(dn[0] * s_light[l][0] + dn[1] * s_light[l][1] + dn[2] * s_light[l][2], 0.0f), 1.0f);
-                    dshade[0] += d * s_light[l][3], dshade[1] += d * s_light[l][4], dshade[2] += d * s_light[l][5];
-                }
-            }
-        }
-        if constexpr (DETAIL) {
-            if (det.grid) det.grid[pix * 2] = gx, det.grid[pix * 2 + 1] = gy;
-        }
-        if (out.alpha) out.alpha[pix] = a;
-        const size_t plane = (size_t)S * S;
-        const size_t o = (size_t)b * 3 * plane + (size_t)i * S + j;
-    #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float bg = background ? background[o + c * plane] : 0.0f;
-            if (!DETAIL || out.shape) {
-                const float shading = __fdiv_rn(shade[c], (float)L);
-                float v = albedo * shading * a + bg * (1.0f - a);
-                if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
-                out.shape[o + c * plane] = v;
-            }
-            if constexpr (DETAIL) {
-                if (det.normal_images) det.normal_images[o + c * plane] = dn[c];
-                if (det.shape_detail) {
-                    const float shading = __fdiv_rn(dshade[c], (float)L);
-                    float v = albedo * shading * a + bg * (1.0f - a);
-                    if (gan_range) v = fminf(fmaxf(v, 0.0f), 1.0f) * 2.0f - 1.0f;
-                    det.shape_detail[o + c * plane] = v;
-                }
+            if (shape) shape[o + c * plane] = blend(shade[c], albedo, a, bg);
+            if (d) {
+                if (d->normal_images) d->normal_images[o + c * plane] = dn[c];
+                if (d->shape_detail) d->shape_detail[o + c * plane] = blend(dshade[c], albedo, a, bg);
             }
         }
     }
+    __device__ __forceinline__ void operator()(const Mesh& m, int b, size_t pix, const Hit& h, const float* s_light) const {
+        if (shape) pixel(m, b, pix, h, s_light, nullptr);
+    }
+};
+
+struct DetailShader : ShapeShader {      // sgdfr_shaperender_detail_f32: the grey panel (shape may be NULL) and the detail panel
+    DetailIO io;
+    __device__ __forceinline__ void operator()(const Mesh& m, int b, size_t pix, const Hit& h, const float* s_light) const {
+        pixel(m, b, pix, h, s_light, &io);
+    }
+};
+
+struct TextureShader {       // sgdfr_shaperender_texture_f32 (SRenderY.forward); every output may be NULL
+    const float* sh_coeff;   // [B,9,3] spherical-harmonic coefficients, or NULL: no shading
+    float sh[9];             // renderer.py:114-119, rounded to float once on the host
+    const float* face_uv;    // [F,3,2]
+    const float* albedo;     // [B,3,Su,Su]
+    int Su;
+    float *images, *albedo_images, *shading, *normal_images, *alpha, *pos_mask, *grid;       // four [B,3,S,S], two [B,1,S,S], [B,S,S,2]
+    static constexpr int kLightFloats = 27;
+
+    __device__ __forceinline__ void prologue(int t, int b, float* s_light) const {      // this image's coefficients [9][3]
+        if (sh_coeff && t < 27) s_light[t] = sh_coeff[(size_t)b * 27 + t];
+    }
+    // an uncovered pixel has every attribute 0, so its shading is add_SHlight(0) and everything else 0
+    __device__ __forceinline__ void operator()(const Mesh& m, int b, size_t pix, const Hit& h, const float* s_light) const {
+        float n[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f}, shd[3] = {0.f, 0.f, 0.f}, tzp = 0.f, gx = 0.f, gy = 0.f;
+        const float a = h.face >= 0 ? 1.0f : 0.0f;
+        if (h.face >= 0) {
+            tzp = normal_at(m, b, h, n);
+            face_uv_at(face_uv, h, gx, gy);
+            if (images || albedo_images) grid_sample3(albedo + (size_t)b * 3 * Su * Su, Su, Su, gx, gy, al);
+        }
+        if (sh_coeff) sh_light(sh, s_light, n, shd);
+        if (grid) grid[pix * 2] = gx, grid[pix * 2 + 1] = gy;
+        if (alpha) alpha[pix] = a;
+        if (pos_mask) pos_mask[pix] = tzp < kPosZ ? 1.0f : 0.0f;
+        const size_t plane = (size_t)m.S * m.S, o = pix + 2 * b * plane;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (images) images[o + c * plane] = (sh_coeff ? al[c] * shd[c] : al[c]) * a;
+            if (albedo_images) albedo_images[o + c * plane] = al[c] * a;
+            if (shading) shading[o + c * plane] = shd[c];
+            if (normal_images) normal_images[o + c * plane] = n[c] * a;
+        }
+    }
+};
+
+struct AttrShader {          // sgdfr_shaperender_attr_f32 (render_normal, render_depth): no normals, no lights
+    const float* values;     // [B,V,D]
+    int D;                   // 1..3
+    float* out;              // [B,D,S,S]; 0 where no face covers
+    static constexpr int kLightFloats = 0;
+
+    __device__ __forceinline__ void prologue(int, int, float*) const {}
+    __device__ __forceinline__ void operator()(const Mesh& m, int b, size_t pix, const Hit& h, const float*) const {
+        const size_t plane = (size_t)m.S * m.S, o = pix + (size_t)(D - 1) * b * plane;
+        for (int c = 0; c < D; ++c)
+            out[o + c * plane] = h.face >= 0 ? mix3(h, values + (size_t)b * m.V * D, corners(m.faces, h.face), D, c) : 0.f;
+    }
+};
+
+template <typename Shader>
+__global__ __launch_bounds__(kChunk) void raster_kernel(const FaceRec* __restrict__ rec, const ushort4* __restrict__ box, int F, Mesh mesh,
+                                                        RasterOut out, Shader shader) {
+    __shared__ float4 s_rec[kChunk][3];
+    __shared__ int s_wave[kChunk / kWave];
+    float* s_light = nullptr;
+    if constexpr (Shader::kLightFloats > 0) {        // the shader's own light table: an instance that stages none holds none
+        __shared__ float s[Shader::kLightFloats];
+        s_light = s;
+    }
+    const int t = threadIdx.x, b = blockIdx.z, S = mesh.S;
+    const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
+    const int j = tx0 + (t & (kTile - 1)), i = ty0 + t / kTile;
+    const bool live = j < S && i < S;
+    const float px = __fdiv_rn((float)(2 * j + 1), (float)S) - 1.0f, py = __fdiv_rn((float)(2 * i + 1), (float)S) - 1.0f;
+    shader.prologue(t, b, s_light);                  // the cover's first barrier orders it before every pixel's read
+    const Hit hit = cover(rec + (size_t)b * F, box + (size_t)b * F, F, t, tx0, ty0, live, px, py, s_rec, s_wave);
+    if (!live) return;
+    const size_t pix = ((size_t)b * S + i) * S + j;
+    write_raster(out, pix, hit);
+    shader(mesh, b, pix, hit, s_light);
 }
 
 int launch_normals(const float* verts, int rows, int V, const int* faces, int F, const int* offsets, const int* entries, int z_only,
@@ -456,9 +448,9 @@ extern "C" int sgdfr_shaperender_normals_f32(const float* vertices, int rows, in
 
 static int forward(const float* vertices, const float* projected, const float* cam, float z_offset, int rows, int V, const int* faces, int F,
                    const int* csr_offsets, const int* csr_entries, int S, const float* lights, int light_rows, int L, const float* background,
-                   int gan_range, float* shape, float* alpha, int* pix_to_face, float* zbuf, float* bary, const DetailIO* det, void* workspace,
-                   int64_t workspace_bytes, void* stream, const TexIO* tex = nullptr, float* normals = nullptr, float* tnormals = nullptr,
-                   const AttrIO* attr = nullptr) {
+                   int gan_range, float* shape, float* alpha, int* pix_to_face, float* zbuf, float* bary, const DetailShader* det, void* workspace,
+                   int64_t workspace_bytes, void* stream, const TextureShader* tex = nullptr, float* normals = nullptr, float* tnormals = nullptr,
+                   const AttrShader* attr = nullptr) {
     SGDFR_REQUIRE(faces, "shaperender_forward: null faces");
     SGDFR_REQUIRE(sizes_ok(rows, V, F), "shaperender_forward: rows=%d V=%d F=%d (rows 1..4096, V and F 1..2^24)", rows, V, F);
     SGDFR_REQUIRE(S >= 1 && S <= kMaxSize, "shaperender_forward: size=%d (1..%d)", S, kMaxSize);
@@ -492,20 +484,21 @@ static int forward(const float* vertices, const float* projected, const float* c
     }
     setup_kernel<<<dim3((F + 255) / 256, rows), 256, 0, st>>>(ws.proj, V, faces, F, S, ws.rec, ws.box);
     if (check_launch("shaperender setup_kernel")) return 1;
-    RasterOut out{shape, alpha, pix_to_face, zbuf, bary};
     const int tiles = (S + kTile - 1) / kTile;
     const dim3 grid(tiles, tiles, rows);
+    const Mesh mesh{faces, V, S, wn, ws.tz};
+    const RasterOut out{pix_to_face, zbuf, bary};
+    DetailShader lit = det ? *det : DetailShader{};    // the grey panel's arguments are the detail shader's base
+    lit.lights = lights, lit.light_rows = light_rows, lit.L = shade ? L : 0, lit.background = background, lit.gan_range = gan_range;
+    lit.shape = shape, lit.alpha = alpha;
     if (tex)
-        raster_kernel<kTexture, TexIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, wn, ws.tz, lights, rows, 0, nullptr, 0, out, *tex);
+        raster_kernel<TextureShader><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, mesh, out, *tex);
     else if (attr)
-        raster_kernel<kAttr, AttrIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, out,
-                                                             *attr);
+        raster_kernel<AttrShader><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, mesh, out, *attr);
     else if (det)
-        raster_kernel<kDetail, DetailIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L, background,
-                                                                 gan_range, out, *det);
+        raster_kernel<DetailShader><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, mesh, out, lit);
     else
-        raster_kernel<kShape, DetailIO><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, S, V, faces, ws.wn, ws.tz, lights, light_rows, L, background,
-                                                                gan_range, out, DetailIO{});
+        raster_kernel<ShapeShader><<<grid, kChunk, 0, st>>>(ws.rec, ws.box, F, mesh, out, lit);
     return check_launch("shaperender raster_kernel");
 }
 
@@ -526,7 +519,9 @@ extern "C" int sgdfr_shaperender_detail_f32(const float* vertices, const float* 
                                             void* workspace, int64_t workspace_bytes, void* stream) {
     SGDFR_REQUIRE(face_uv && uv_normals, "shaperender_detail: null face_uv or uv_normals");
     SGDFR_REQUIRE(Su >= 1 && Su <= kMaxSize, "shaperender_detail: uv_size=%d (1..%d)", Su, kMaxSize);
-    const DetailIO det{face_uv, uv_normals, Su, shape_detail, grid, detail_normal_images};
+    DetailShader det{};
+    det.io.face_uv = face_uv, det.io.uv_normals = uv_normals, det.io.Su = Su;
+    det.io.shape_detail = shape_detail, det.io.grid = grid, det.io.normal_images = detail_normal_images;
     return forward(vertices, projected, cam, z_offset, rows, V, faces, F, csr_offsets, csr_entries, S, lights, light_rows, L, background,
                    gan_range, shape, alpha, pix_to_face, zbuf, bary, &det, workspace, workspace_bytes, stream);
 }
@@ -544,9 +539,12 @@ extern "C" int sgdfr_shaperender_texture_f32(const float* vertices, const float*
     SGDFR_REQUIRE(images || albedo_images || alpha_images || pos_mask || shading_images || grid || normal_images || normals ||
                       transformed_normals || pix_to_face || zbuf || bary,
                   "shaperender_texture: no output");
-    TexIO tex{face_uv, albedo, Su, {}, images, albedo_images, alpha_images, pos_mask, shading_images, grid, normal_images};
+    TextureShader tex{};
+    tex.sh_coeff = sh_lights, tex.face_uv = face_uv, tex.albedo = albedo, tex.Su = Su;
     for (int k = 0; k < 9; ++k) tex.sh[k] = sh_constants[k];
-    return forward(vertices, projected, cam, z_offset, rows, V, faces, F, csr_offsets, csr_entries, S, sh_lights, rows, 0, nullptr, 0, nullptr,
+    tex.images = images, tex.albedo_images = albedo_images, tex.alpha = alpha_images, tex.pos_mask = pos_mask, tex.shading = shading_images;
+    tex.grid = grid, tex.normal_images = normal_images;
+    return forward(vertices, projected, cam, z_offset, rows, V, faces, F, csr_offsets, csr_entries, S, nullptr, 0, 0, nullptr, 0, nullptr,
                    nullptr, pix_to_face, zbuf, bary, nullptr, workspace, workspace_bytes, stream, &tex, normals, transformed_normals);
 }
 
@@ -554,7 +552,7 @@ extern "C" int sgdfr_shaperender_attr_f32(const float* projected, float z_offset
                                           const float* values, int D, float* out, int* pix_to_face, float* zbuf, float* bary, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
     SGDFR_REQUIRE(projected, "shaperender_attr: null projected");
-    const AttrIO attr{values, D, out};
+    const AttrShader attr{values, D, out};
     return forward(nullptr, projected, nullptr, z_offset, rows, V, faces, F, nullptr, nullptr, S, nullptr, 0, 0, nullptr, 0, nullptr, nullptr,
                    pix_to_face, zbuf, bary, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, &attr);
 }

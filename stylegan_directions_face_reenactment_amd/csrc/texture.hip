@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "mesh_sample.h"
 
 #pragma clang fp contract(off)
 
@@ -143,56 +144,18 @@ struct UvTexIO {
     float* uv_gt;              // [B,3,S,S] or NULL
 };
 
-// F.grid_sample(bilinear, zeros, align_corners=False) of one [3,H,W] image at g: a neighbour outside adds nothing
-__device__ __forceinline__ void sample_image(const float* __restrict__ img, int H, int W, float gx, float gy, float (&r)[3]) {
-    const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f, iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    const float ax = ix - fx, ay = iy - fy, bx = (fx + 1.0f) - ix, by = (fy + 1.0f) - iy;
-    r[0] = r[1] = r[2] = 0.f;
-    if (!(fx >= -1.0f && fx < (float)W && fy >= -1.0f && fy < (float)H)) return;       // not finite or far outside: no cast is made
-    const int x0 = (int)fx, y0 = (int)fy;
-    const size_t plane = (size_t)H * W;
-    const float w[4] = {bx * by, ax * by, bx * ay, ax * ay};      // nw, ne, sw, se
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x = x0 + (k & 1), y = y0 + (k >> 1);
-        if (x < 0 || x >= W || y < 0 || y >= H) continue;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) r[c] += img[c * plane + (size_t)y * W + x] * w[k];
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void uvtexture_kernel(int V, int F, int S, UvTexIO io) {
     const int b = blockIdx.y, t = blockIdx.x * kThreads + threadIdx.x, plane = S * S;
     if (t >= plane) return;
     const size_t o = (size_t)b * 3 * plane + t;
-    float n[3], sh[3] = {0.f, 0.f, 0.f};
+    float n[3], sh[3], p[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) n[c] = io.uv_normals[o + (size_t)c * plane];
-    {   // add_SHlight: sum_k light[k][c] (basis_k constant_k), k ascending
-        const float basis[9] = {1.0f, n[0], n[1], n[2], n[0] * n[1], n[0] * n[2], n[1] * n[2], n[0] * n[0] - n[1] * n[1],
-                                3.0f * (n[2] * n[2]) - 1.0f};
-        const float* l = io.light + (size_t)b * 27;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const float v = basis[k] * io.sh[k];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) sh[c] += l[k * 3 + c] * v;
-        }
-    }
-    float p[3] = {0.f, 0.f, 0.f};                                        // world2uv(trans_verts): (0, 0) where no face covers
-    const unsigned f = (unsigned)io.pix_to_face[t];
-    if (f < (unsigned)F) {
-        const unsigned i0 = (unsigned)io.faces[f * 3], i1 = (unsigned)io.faces[f * 3 + 1], i2 = (unsigned)io.faces[f * 3 + 2];
-        if (i0 < (unsigned)V && i1 < (unsigned)V && i2 < (unsigned)V) {
-            const float* tv = io.trans_verts + (size_t)b * V * 3;
-            const float w0 = io.bary[t * 3], w1 = io.bary[t * 3 + 1], w2 = io.bary[t * 3 + 2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) p[c] = w0 * tv[i0 * 3 + c] + w1 * tv[i1 * 3 + c] + w2 * tv[i2 * 3 + c];
-        }
-    }
+    sh_light(io.sh, io.light + (size_t)b * 27, n, sh);
+    // world2uv(trans_verts): (0, 0) where no face covers
+    bary_gather3(io.trans_verts + (size_t)b * V * 3, V, io.faces, F, io.pix_to_face, io.bary, t, p);
     float gt[3] = {0.f, 0.f, 0.f};
-    if (io.uv_texture_gt || io.uv_gt) sample_image(io.images + (size_t)b * 3 * io.H * io.W, io.H, io.W, p[0], p[1], gt);
+    if (io.uv_texture_gt || io.uv_gt) grid_sample3(io.images + (size_t)b * 3 * io.H * io.W, io.H, io.W, p[0], p[1], gt);
     const float m = io.mask[t];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

@@ -25,7 +25,7 @@ from torch import nn
 
 from . import _native as N
 from .packs import PackedWeights, views
-from .shape_render import MeshTopology, render_shape, vertex_normals, rasterize
+from .shape_render import MeshTopology, _check_device, _check_map, _check_vertices, render_shape, vertex_normals, rasterize
 
 LATENT, UV_SIZE = N.DETAIL_LATENT, N.DETAIL_UV_SIZE
 _CHANNELS = ((128, 128), (128, 64), (64, 64), (64, 32), (32, 16))       # the five up + conv layers
@@ -87,15 +87,10 @@ def tap_views(taps, rows):
 
 
 def _check_latent(latent):
-    if not torch.is_tensor(latent):
-        raise RuntimeError('DetailDecoder: latent must be a tensor, got %s' % type(latent))
-    N.require_device(latent)
-    if latent.ndim != 2 or latent.shape[0] < 1 or latent.shape[1] != LATENT:
-        raise RuntimeError('DetailDecoder: expected a latent of shape [B,%d] = cat(pose[:, 3:], exp, detail), got %s'
-                           % (LATENT, tuple(latent.shape)))
+    z = _check_map('DetailDecoder', 'latent', latent, (None, LATENT), 'a latent of shape [B,%d] = cat(pose[:, 3:], exp, detail)' % LATENT)
     if torch.is_grad_enabled() and latent.requires_grad:
         raise RuntimeError('DetailDecoder: the detail path is forward only; call it under torch.no_grad() or on a detached latent')
-    return N.f32c(latent.detach())
+    return z
 
 
 def decode_uv(D, latent, taps=False):
@@ -229,19 +224,10 @@ def _check_layout(who, layout):
         raise RuntimeError('%s: layout must be a UvLayout, got %s' % (who, type(layout)))
 
 
-def _check_values(who, name, t, layout, rows=None):
-    if not torch.is_tensor(t):
-        raise RuntimeError('%s: %s must be a tensor, got %s' % (who, name, type(t)))
-    N.require_device(t)
-    if t.ndim != 3 or t.shape[0] < 1 or tuple(t.shape[1:]) != (layout.n_vertices, 3) or (rows is not None and t.shape[0] != rows):
-        raise RuntimeError('%s: expected %s of shape [%s,%d,3], got %s' % (who, name, 'B' if rows is None else rows, layout.n_vertices, tuple(t.shape)))
-    return N.f32c(t.detach())
-
-
 def world2uv(layout, values):
     """SRenderY.world2uv: per-vertex values [B,V,3] -> [B,3,S,S]; per texel sum_k bary_k values[faces[f][k]], 0 where no face covers."""
     _check_layout('world2uv', layout)
-    v = _check_values('world2uv', 'values', values, layout)
+    v = _check_vertices('world2uv', 'values', values, layout.n_vertices)
     faces, pix, bary, _, _, _ = layout.tables(v.device)
     S = layout.uv_size
     out = torch.empty((v.shape[0], 3, S, S), dtype=torch.float32, device=v.device)
@@ -255,17 +241,11 @@ def detail_normals(layout, uv_z, verts, normals, dense_vertices=False):
     launch; dense_vertices=True: (uv_detail_normals, dense vertices [B,S*S,3]) -- displacement2vertex's, over layout.dense_faces."""
     who = 'detail_normals'
     _check_layout(who, layout)
-    v = _check_values(who, 'verts', verts, layout)
-    n = _check_values(who, 'normals', normals, layout, v.shape[0])
+    v = _check_vertices(who, 'verts', verts, layout.n_vertices)
+    n = _check_vertices(who, 'normals', normals, layout.n_vertices, v.shape[0])
     S, B = layout.uv_size, v.shape[0]
-    if not torch.is_tensor(uv_z):
-        raise RuntimeError('%s: uv_z must be a tensor, got %s' % (who, type(uv_z)))
-    N.require_device(uv_z)
-    if tuple(uv_z.shape) != (B, 1, S, S):
-        raise RuntimeError('%s: expected uv_z of shape [%d,1,%d,%d], got %s' % (who, B, S, S, tuple(uv_z.shape)))
-    if uv_z.device != v.device or n.device != v.device:
-        raise RuntimeError('%s: all tensors must live on the vertices\' device %s' % (who, v.device))
-    z = N.f32c(uv_z.detach())
+    z = _check_map(who, 'uv_z', uv_z, (B, 1, S, S))
+    _check_device(who, v.device, z, n)
     faces, pix, bary, mask, fixed, _ = layout.tables(v.device)
     out = torch.empty((B, 3, S, S), dtype=torch.float32, device=v.device)
     dense = torch.empty((B, S * S, 3), dtype=torch.float32, device=v.device) if dense_vertices else None

@@ -89,18 +89,64 @@ def _check_topology(who, topo):
         raise RuntimeError('%s: topo must be a MeshTopology, got %s' % (who, type(topo)))
 
 
-def _check_vertices(who, name, t, topo, rows=None):
+def _check_map(who, name, t, shape, text=None):
+    """The one tensor check: t must be a tensor on a GPU whose shape fits `shape` -- per dimension an int, None (any size >= 1) or a
+    container of the sizes allowed -> t detached, float32, contiguous.  `text` words the expectation where the plain list does not."""
     if not torch.is_tensor(t):
         raise RuntimeError('%s: %s must be a tensor, got %s' % (who, name, type(t)))
     N.require_device(t)
-    if t.ndim != 3 or t.shape[0] < 1 or tuple(t.shape[1:]) != (topo.n_vertices, 3) or (rows is not None and t.shape[0] != rows):
-        raise RuntimeError('%s: expected %s of shape [%s,%d,3], got %s' % (who, name, 'B' if rows is None else rows, topo.n_vertices, tuple(t.shape)))
+    fits = lambda n, s: n >= 1 if s is None else n == s if isinstance(s, int) else n in s
+    if t.ndim != len(shape) or not all(fits(n, s) for n, s in zip(t.shape, shape)):
+        raise RuntimeError('%s: expected %s, got %s' % (who, text or '%s of shape [%s]' % (name, ','.join(map(str, shape))), tuple(t.shape)))
     return N.f32c(t.detach())
+
+
+def _check_vertices(who, name, t, n_vertices, rows=None):
+    return _check_map(who, name, t, (rows, n_vertices, 3), '%s of shape [%s,%d,3]' % (name, 'B' if rows is None else rows, n_vertices))
 
 
 def _check_size(who, size):
     if isinstance(size, bool) or not isinstance(size, int) or not 1 <= size <= N.SHAPERENDER_MAX_SIZE:
         raise RuntimeError('%s: size must be an int in 1..%d, got %r' % (who, N.SHAPERENDER_MAX_SIZE, size))
+
+
+def _prepare(who, vertices, topo, cam, projected, size):
+    """What the renderers check first: the topology, exactly one of cam / projected beside world vertices (vertices None: projected
+    alone), the size, one device -> (vertices, cam, projected) checked as _check_map returns them, the batch and the device."""
+    _check_topology(who, topo)
+    if vertices is not None and (cam is None) == (projected is None):
+        raise RuntimeError('%s: exactly one of cam and projected must be given' % who)
+    if vertices is None:
+        v, projected = None, _check_vertices(who, 'projected', projected, topo.n_vertices)
+    else:
+        v = _check_vertices(who, 'vertices', vertices, topo.n_vertices)
+    _check_size(who, size)
+    lead = projected if v is None else v
+    if cam is not None:
+        cam = _check_map(who, 'cam', cam, (lead.shape[0], 3))
+    elif v is not None:
+        projected = _check_vertices(who, 'projected', projected, topo.n_vertices, lead.shape[0])
+    _check_device(who, lead.device, cam, projected)
+    return v, cam, projected, lead.shape[0], lead.device
+
+
+def _check_device(who, device, *tensors):
+    if any(t is not None and t.device != device for t in tensors):
+        raise RuntimeError('%s: all tensors must live on the vertices\' device %s' % (who, device))
+
+
+def _check_mesh_layout(who, layout, topo):
+    from .detail import UvLayout
+    if not isinstance(layout, UvLayout):
+        raise RuntimeError('%s: layout must be a detail.UvLayout, got %s' % (who, type(layout)))
+    if layout.n_faces != topo.n_faces or layout.n_vertices != topo.n_vertices:
+        raise RuntimeError('%s: the layout is for a mesh of %d vertices and %d faces, topo has %d and %d'
+                           % (who, layout.n_vertices, layout.n_faces, topo.n_vertices, topo.n_faces))
+
+
+def _alloc(want, shapes, device):
+    """The output dict: an empty tensor for every name of `shapes` that `want` holds, in the order of `shapes`."""
+    return {k: torch.empty(s, dtype=torch.int32 if k == 'pix_to_face' else torch.float32, device=device) for k, s in shapes.items() if k in want}
 
 
 def _workspace(rows, topo, device):
@@ -111,7 +157,7 @@ def _workspace(rows, topo, device):
 def vertex_normals(vertices, topo):
     """util.vertex_normals: vertices [B,V,3] -> unit normals [B,V,3] (zeros for a vertex no face names)."""
     _check_topology('vertex_normals', topo)
-    v = _check_vertices('vertex_normals', 'vertices', vertices, topo)
+    v = _check_vertices('vertex_normals', 'vertices', vertices, topo.n_vertices)
     faces, offsets, entries = topo.tables(v.device)
     out = torch.empty_like(v)
     N.call('sgdfr_shaperender_normals_f32', N.ptr(v), v.shape[0], topo.n_vertices, N.ptr(faces), topo.n_faces, N.ptr(offsets), N.ptr(entries),
@@ -123,18 +169,13 @@ def rasterize(projected, topo, size):
     """rasterize_meshes at blur_radius 0, one face per pixel, no perspective correction, with the x, y flip of renderer.py:53 folded
     in: projected [B,V,3] in normalised image space (+x right, +y down, smaller z nearer) -> (pix_to_face [B,S,S] int32, -1 where no
     face covers, the index counting within the mesh; zbuf [B,S,S]; bary [B,S,S,3]; both -1 where no face covers)."""
-    _check_topology('rasterize', topo)
-    p = _check_vertices('rasterize', 'projected', projected, topo)
-    _check_size('rasterize', size)
-    B, dev = p.shape[0], p.device
+    _, _, p, B, dev = _prepare('rasterize', None, topo, None, projected, size)
     faces, _, _ = topo.tables(dev)
-    pix = torch.empty((B, size, size), dtype=torch.int32, device=dev)
-    zbuf = torch.empty((B, size, size), dtype=torch.float32, device=dev)
-    bary = torch.empty((B, size, size, 3), dtype=torch.float32, device=dev)
+    out = _alloc(_WANT, {'pix_to_face': (B, size, size), 'zbuf': (B, size, size), 'bary': (B, size, size, 3)}, dev)
     ws, nbytes = _workspace(B, topo, dev)
     N.call('sgdfr_shaperender_forward_f32', None, N.ptr(p), None, 0.0, B, topo.n_vertices, N.ptr(faces), topo.n_faces, None, None, size,
-           None, 0, 0, None, 0, None, None, N.ptr(pix), N.ptr(zbuf), N.ptr(bary), N.ptr(ws), nbytes, N.stream())
-    return pix, zbuf, bary
+           None, 0, 0, None, 0, None, None, N.ptr(out['pix_to_face']), N.ptr(out['zbuf']), N.ptr(out['bary']), N.ptr(ws), nbytes, N.stream())
+    return out['pix_to_face'], out['zbuf'], out['bary']
 
 
 _LIGHTS = {}
@@ -168,94 +209,37 @@ def render_shape(vertices, topo, cam=None, projected=None, size=224, images=None
     if (layout is None) != (detail_normals is None):
         raise RuntimeError('%s: layout and detail_normals must be given together' % who)
     detail = layout is not None
-    if detail:
-        if 'shape' not in want or any(w not in _WANT + _WANT_DETAIL for w in want):
-            raise RuntimeError("%s: want must name 'shape' and any of %s, got %r" % (who, _WANT[1:] + _WANT_DETAIL, want))
-    elif 'shape' not in want or any(w not in _WANT for w in want):
-        raise RuntimeError("%s: want must name 'shape' and any of %s, got %r" % (who, _WANT[1:], want))
-    if (cam is None) == (projected is None):
-        raise RuntimeError('%s: exactly one of cam and projected must be given' % who)
-    v = _check_vertices(who, 'vertices', vertices, topo)
-    _check_size(who, size)
-    B, dev = v.shape[0], v.device
-    if cam is not None:
-        if not torch.is_tensor(cam):
-            raise RuntimeError('%s: cam must be a tensor, got %s' % (who, type(cam)))
-        N.require_device(cam)
-        if tuple(cam.shape) != (B, 3):
-            raise RuntimeError('%s: expected cam of shape [%d,3], got %s' % (who, B, tuple(cam.shape)))
-        cam = N.f32c(cam.detach())
-    else:
-        projected = _check_vertices(who, 'projected', projected, topo, B)
+    allowed = _WANT + _WANT_DETAIL if detail else _WANT
+    if 'shape' not in want or any(w not in allowed for w in want):
+        raise RuntimeError("%s: want must name 'shape' and any of %s, got %r" % (who, allowed[1:], want))
+    v, cam, projected, B, dev = _prepare(who, vertices, topo, cam, projected, size)
+    S, MAXL = size, N.SHAPERENDER_MAX_LIGHTS
     if images is not None:
-        if not torch.is_tensor(images):
-            raise RuntimeError('%s: images must be a tensor, got %s' % (who, type(images)))
-        N.require_device(images)
-        if tuple(images.shape) != (B, 3, size, size):
-            raise RuntimeError('%s: expected images of shape [%d,3,%d,%d], got %s' % (who, B, size, size, tuple(images.shape)))
-        images = N.f32c(images.detach())
-    if lights is None:
-        lights = _default_lights(dev)
-    else:
-        if not torch.is_tensor(lights):
-            raise RuntimeError('%s: lights must be a tensor, got %s' % (who, type(lights)))
-        N.require_device(lights)
-        if lights.ndim != 3 or lights.shape[0] not in (1, B) or not 1 <= lights.shape[1] <= N.SHAPERENDER_MAX_LIGHTS or lights.shape[2] != 6:
-            raise RuntimeError('%s: expected lights of shape [1 or %d, 1..%d, 6], got %s' % (who, B, N.SHAPERENDER_MAX_LIGHTS, tuple(lights.shape)))
-        lights = N.f32c(lights.detach())
+        images = _check_map(who, 'images', images, (B, 3, S, S))
+    lights = _default_lights(dev) if lights is None else _check_map(who, 'lights', lights, ((1, B), range(1, MAXL + 1), 6),
+                                                                    'lights of shape [1 or %d, 1..%d, 6]' % (B, MAXL))
     if detail:
-        from .detail import UvLayout
-        if not isinstance(layout, UvLayout):
-            raise RuntimeError('%s: layout must be a detail.UvLayout, got %s' % (who, type(layout)))
-        if layout.n_faces != topo.n_faces or layout.n_vertices != topo.n_vertices:
-            raise RuntimeError('%s: the layout is for a mesh of %d vertices and %d faces, topo has %d and %d'
-                               % (who, layout.n_vertices, layout.n_faces, topo.n_vertices, topo.n_faces))
-        if not torch.is_tensor(detail_normals):
-            raise RuntimeError('%s: detail_normals must be a tensor, got %s' % (who, type(detail_normals)))
-        N.require_device(detail_normals)
-        Su = layout.uv_size
-        if tuple(detail_normals.shape) != (B, 3, Su, Su):
-            raise RuntimeError('%s: expected detail_normals of shape [%d,3,%d,%d], got %s' % (who, B, Su, Su, tuple(detail_normals.shape)))
-        detail_normals = N.f32c(detail_normals.detach())
-    if any(t is not None and t.device != dev for t in (cam, projected, images, lights, detail_normals)):
-        raise RuntimeError('%s: all tensors must live on the vertices\' device %s' % (who, dev))
+        _check_mesh_layout(who, layout, topo)
+        detail_normals = _check_map(who, 'detail_normals', detail_normals, (B, 3, layout.uv_size, layout.uv_size))
+    _check_device(who, dev, images, lights, detail_normals)
     faces, offsets, entries = topo.tables(dev)
-    out = {'shape': torch.empty((B, 3, size, size), dtype=torch.float32, device=dev)}
-    for name, shape, dtype in (('alpha', (B, 1, size, size), torch.float32), ('pix_to_face', (B, size, size), torch.int32),
-                               ('zbuf', (B, size, size), torch.float32), ('bary', (B, size, size, 3), torch.float32)):
-        if name in want:
-            out[name] = torch.empty(shape, dtype=dtype, device=dev)
+    out = _alloc(want, {'shape': (B, 3, S, S), 'alpha': (B, 1, S, S), 'pix_to_face': (B, S, S), 'zbuf': (B, S, S), 'bary': (B, S, S, 3),
+                        'shape_detail': (B, 3, S, S), 'grid': (B, S, S, 2), 'detail_normal_images': (B, 3, S, S)}, dev)
     ws, nbytes = _workspace(B, topo, dev)
+    head = (N.ptr(v), N.ptr(projected), N.ptr(cam), Z_OFFSET, B, topo.n_vertices, N.ptr(faces), topo.n_faces, N.ptr(offsets), N.ptr(entries), S,
+            N.ptr(lights), lights.shape[0], lights.shape[1], N.ptr(images), int(bool(gan_range)))
+    tail = (N.ptr(out.get('alpha')), N.ptr(out.get('pix_to_face')), N.ptr(out.get('zbuf')), N.ptr(out.get('bary')), N.ptr(ws), nbytes, N.stream())
     if detail:
-        for name, shape in (('shape_detail', (B, 3, size, size)), ('grid', (B, size, size, 2)), ('detail_normal_images', (B, 3, size, size))):
-            if name in want:
-                out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
-        face_uv = layout.tables(dev)[5]
-        N.call('sgdfr_shaperender_detail_f32', N.ptr(v), N.ptr(projected), N.ptr(cam), Z_OFFSET, B, topo.n_vertices, N.ptr(faces), topo.n_faces,
-               N.ptr(offsets), N.ptr(entries), size, N.ptr(lights), lights.shape[0], lights.shape[1], N.ptr(images), int(bool(gan_range)),
-               N.ptr(face_uv), N.ptr(detail_normals), layout.uv_size, N.ptr(out['shape']), N.ptr(out.get('shape_detail')), N.ptr(out.get('grid')),
-               N.ptr(out.get('detail_normal_images')), N.ptr(out.get('alpha')), N.ptr(out.get('pix_to_face')), N.ptr(out.get('zbuf')),
-               N.ptr(out.get('bary')), N.ptr(ws), nbytes, N.stream())
-        return out
-    N.call('sgdfr_shaperender_forward_f32', N.ptr(v), N.ptr(projected), N.ptr(cam), Z_OFFSET, B, topo.n_vertices, N.ptr(faces), topo.n_faces,
-           N.ptr(offsets), N.ptr(entries), size, N.ptr(lights), lights.shape[0], lights.shape[1], N.ptr(images), int(bool(gan_range)),
-           N.ptr(out['shape']), N.ptr(out.get('alpha')), N.ptr(out.get('pix_to_face')), N.ptr(out.get('zbuf')), N.ptr(out.get('bary')),
-           N.ptr(ws), nbytes, N.stream())
+        N.call('sgdfr_shaperender_detail_f32', *head, N.ptr(layout.tables(dev)[5]), N.ptr(detail_normals), layout.uv_size, N.ptr(out['shape']),
+               N.ptr(out.get('shape_detail')), N.ptr(out.get('grid')), N.ptr(out.get('detail_normal_images')), *tail)
+    else:
+        N.call('sgdfr_shaperender_forward_f32', *head, N.ptr(out['shape']), *tail)
     return out
 
 
 def _forward_only(who, *tensors):
     if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors):
         raise RuntimeError('%s: forward only (no gradient reaches its inputs); call it under torch.no_grad() or on detached tensors' % who)
-
-
-def _check_map(who, name, t, shape):
-    if not torch.is_tensor(t):
-        raise RuntimeError('%s: %s must be a tensor, got %s' % (who, name, type(t)))
-    N.require_device(t)
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError('%s: expected %s of shape [%s], got %s' % (who, name, ','.join(map(str, shape)), tuple(t.shape)))
-    return N.f32c(t.detach())
 
 
 def sh_constants():
@@ -282,22 +266,10 @@ def render_texture(vertices, topo, layout, albedo, lights=None, cam=None, projec
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in _WANT_TEXTURE for w in want):
         raise RuntimeError('%s: want must name at least one of %s, got %r' % (who, _WANT_TEXTURE, want))
-    if (cam is None) == (projected is None):
-        raise RuntimeError('%s: exactly one of cam and projected must be given' % who)
-    from .detail import UvLayout
-    if not isinstance(layout, UvLayout):
-        raise RuntimeError('%s: layout must be a detail.UvLayout, got %s' % (who, type(layout)))
-    if layout.n_faces != topo.n_faces or layout.n_vertices != topo.n_vertices:
-        raise RuntimeError('%s: the layout is for a mesh of %d vertices and %d faces, topo has %d and %d'
-                           % (who, layout.n_vertices, layout.n_faces, topo.n_vertices, topo.n_faces))
     _forward_only(who, vertices, albedo, lights, cam, projected)
-    v = _check_vertices(who, 'vertices', vertices, topo)
-    _check_size(who, size)
-    B, dev, Su = v.shape[0], v.device, layout.uv_size
-    if cam is not None:
-        cam = _check_map(who, 'cam', cam, (B, 3))
-    else:
-        projected = _check_vertices(who, 'projected', projected, topo, B)
+    v, cam, projected, B, dev = _prepare(who, vertices, topo, cam, projected, size)
+    _check_mesh_layout(who, layout, topo)
+    Su = layout.uv_size
     if albedo is None:
         if 'images' in want or 'albedo_images' in want:
             raise RuntimeError("%s: 'images' and 'albedo_images' need an albedo" % who)
@@ -307,14 +279,12 @@ def render_texture(vertices, topo, layout, albedo, lights=None, cam=None, projec
         if torch.is_tensor(lights) and lights.ndim == 3 and lights.shape[2] == 6:
             raise RuntimeError('%s: point and directional lights [B,L,6] have no HIP kernel here; pass spherical-harmonic lights [B,9,3]' % who)
         lights = _check_map(who, 'lights', lights, (B, 9, 3))
-    if any(t is not None and t.device != dev for t in (cam, projected, albedo, lights)):
-        raise RuntimeError('%s: all tensors must live on the vertices\' device %s' % (who, dev))
+    _check_device(who, dev, albedo, lights)
     faces, offsets, entries = topo.tables(dev)
     V, S = topo.n_vertices, size
-    shapes = {'images': (B, 3, S, S), 'albedo_images': (B, 3, S, S), 'alpha_images': (B, 1, S, S), 'pos_mask': (B, 1, S, S),
-              'shading_images': (B, 3, S, S), 'grid': (B, S, S, 2), 'normal_images': (B, 3, S, S), 'normals': (B, V, 3),
-              'transformed_normals': (B, V, 3), 'pix_to_face': (B, S, S), 'zbuf': (B, S, S), 'bary': (B, S, S, 3)}
-    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == 'pix_to_face' else torch.float32, device=dev) for k in _WANT_TEXTURE if k in want}
+    out = _alloc(want, {'images': (B, 3, S, S), 'albedo_images': (B, 3, S, S), 'alpha_images': (B, 1, S, S), 'pos_mask': (B, 1, S, S),
+                        'shading_images': (B, 3, S, S), 'grid': (B, S, S, 2), 'normal_images': (B, 3, S, S), 'normals': (B, V, 3),
+                        'transformed_normals': (B, V, 3), 'pix_to_face': (B, S, S), 'zbuf': (B, S, S), 'bary': (B, S, S, 3)}, dev)
     ws, nbytes = _workspace(B, topo, dev)
     face_uv = layout.tables(dev)[5]
     N.call('sgdfr_shaperender_texture_f32', N.ptr(v), N.ptr(projected), N.ptr(cam), Z_OFFSET, B, V, N.ptr(faces), topo.n_faces, N.ptr(offsets),
@@ -324,23 +294,16 @@ def render_texture(vertices, topo, layout, albedo, lights=None, cam=None, projec
 
 
 def _render_attr(who, projected, values, topo, size, z_offset):
-    _check_topology(who, topo)
     _forward_only(who, projected, values)
-    p = _check_vertices(who, 'projected', projected, topo)
-    _check_size(who, size)
-    if not torch.is_tensor(values):
-        raise RuntimeError('%s: the per-vertex values must be a tensor, got %s' % (who, type(values)))
-    N.require_device(values)
-    B, V = p.shape[0], topo.n_vertices
-    if values.ndim != 3 or tuple(values.shape[:2]) != (B, V) or not 1 <= values.shape[2] <= 3:
-        raise RuntimeError('%s: expected per-vertex values of shape [%d,%d,1..3], got %s' % (who, B, V, tuple(values.shape)))
-    if values.device != p.device:
+    _, _, p, B, dev = _prepare(who, None, topo, None, projected, size)
+    V = topo.n_vertices
+    a = _check_map(who, 'the per-vertex values', values, (B, V, (1, 2, 3)), 'per-vertex values of shape [%d,%d,1..3]' % (B, V))
+    if a.device != dev:
         raise RuntimeError('%s: all tensors must live on one device' % who)
-    a = N.f32c(values.detach())
     D = a.shape[2]
-    faces, _, _ = topo.tables(p.device)
-    out = torch.empty((B, D, size, size), dtype=torch.float32, device=p.device)
-    ws, nbytes = _workspace(B, topo, p.device)
+    faces, _, _ = topo.tables(dev)
+    out = torch.empty((B, D, size, size), dtype=torch.float32, device=dev)
+    ws, nbytes = _workspace(B, topo, dev)
     N.call('sgdfr_shaperender_attr_f32', N.ptr(p), float(z_offset), B, V, N.ptr(faces), topo.n_faces, size, N.ptr(a), D, N.ptr(out), None, None,
            None, N.ptr(ws), nbytes, N.stream())
     return out
@@ -358,9 +321,8 @@ def render_depth(projected, topo, size=224):
     where no face covers.  The minimum and maximum over the batch are torch reductions on the device in front of the launch (no host
     synchronisation); the vertices are rasterised at z - min(z) + 10, and the caller's tensor is not modified."""
     who = 'render_depth'
-    _check_topology(who, topo)
     _forward_only(who, projected)
-    p = _check_vertices(who, 'projected', projected, topo)
+    p = _prepare(who, None, topo, None, projected, size)[2]
     z = p[:, :, 2:] - p[:, :, 2].min()
     d = -z
     d = d - d.min()

@@ -19,7 +19,7 @@ from torch import nn
 
 from . import _native as N
 from .packs import PackedWeights
-from .shape_render import _check_map, _check_size, _forward_only, render_texture, sh_constants
+from .shape_render import _check_map, _check_size, _check_vertices, _forward_only, render_texture, sh_constants
 
 _WANT_UV = ('uv_shading', 'uv_texture', 'uv_texture_gt', 'uv_pverts', 'uv_gt')
 
@@ -91,37 +91,27 @@ class FlameTex(PackedWeights, nn.Module):
         return pack[:P].view(3, uv, uv), pack[P:].view(self.n_tex, 3, uv, uv)
 
     def forward(self, texcode):
-        if not torch.is_tensor(texcode):
-            raise RuntimeError('FlameTex: texcode must be a tensor, got %s' % type(texcode))
-        N.require_device(texcode)
-        if texcode.ndim != 2 or texcode.shape[0] < 1 or texcode.shape[1] != self.n_tex:
-            raise RuntimeError('FlameTex: expected texcode of shape [B,%d], got %s' % (self.n_tex, tuple(texcode.shape)))
-        if texcode.shape[0] > 4096:
-            raise RuntimeError('FlameTex: unsupported batch of %d rows (1..4096)' % texcode.shape[0])
+        code = _check_map('FlameTex', 'texcode', texcode, (None, self.n_tex), 'texcode of shape [B,%d]' % self.n_tex)
+        if code.shape[0] > 4096:
+            raise RuntimeError('FlameTex: unsupported batch of %d rows (1..4096)' % code.shape[0])
         _forward_only('FlameTex', texcode)
-        if texcode.device != self.texture_mean.device:
-            raise RuntimeError('FlameTex: texcode lives on %s, the texture space on %s' % (texcode.device, self.texture_mean.device))
-        code = N.f32c(texcode.detach())
+        if code.device != self.texture_mean.device:
+            raise RuntimeError('FlameTex: texcode lives on %s, the texture space on %s' % (code.device, self.texture_mean.device))
         out = torch.empty((code.shape[0], 3, self.uv_size, self.uv_size), dtype=torch.float32, device=code.device)
         N.call('sgdfr_flametex_forward_f32', N.ptr(code), code.shape[0], N.ptr(self.packed()), self.uv_size, self.n_tex, N.ptr(out), N.stream())
         return out
 
 
 def _check_uv_args(who, layout, albedo, uv_detail_normals, light, trans_verts, images):
-    from .detail import _check_layout, _check_values
+    from .detail import _check_layout
     _check_layout(who, layout)
     _forward_only(who, albedo, uv_detail_normals, light, trans_verts, images)
-    tv = _check_values(who, 'trans_verts', trans_verts, layout)
+    tv = _check_vertices(who, 'trans_verts', trans_verts, layout.n_vertices)
     B, S = tv.shape[0], layout.uv_size
     n = _check_map(who, 'uv_detail_normals', uv_detail_normals, (B, 3, S, S))
     a = None if albedo is None else _check_map(who, 'albedo', albedo, (B, 3, S, S))
     l = _check_map(who, 'light', light, (B, 9, 3))
-    if not torch.is_tensor(images):
-        raise RuntimeError('%s: images must be a tensor, got %s' % (who, type(images)))
-    N.require_device(images)
-    if images.ndim != 4 or tuple(images.shape[:2]) != (B, 3) or not (1 <= images.shape[2] <= 4096 and 1 <= images.shape[3] <= 4096):
-        raise RuntimeError('%s: expected images of shape [%d,3,H,W] with sides 1..4096, got %s' % (who, B, tuple(images.shape)))
-    im = N.f32c(images.detach())
+    im = _check_map(who, 'images', images, (B, 3, range(1, 4097), range(1, 4097)), 'images of shape [%d,3,H,W] with sides 1..4096' % B)
     if any(t is not None and t.device != tv.device for t in (n, a, l, im)):
         raise RuntimeError('%s: all tensors must live on one device' % who)
     return tv, n, a, l, im
