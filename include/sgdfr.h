@@ -556,6 +556,24 @@ int sgdfr_sweep_rows_host(const struct sgdfr_sweep_record* records, const struct
 int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const int* is_start, const float* src, int64_t src_bstride,
                            float* pooled, float* bordered, unsigned char* frames, int panels, void* stream);
 
+/* The pooled image loss of PTI above 256^2 (what libs/optimization.py:50-58 has to compare is the image generic.py:146-148 hands
+ * out, AdaptiveAvgPool2d((256,256)) of the generator's): x [B,3,P*f,P*f] float32, real [B,3,P,P], f = 1, 2 or 4, 1 <= P <= 8192,
+ * 1 <= B <= 4096.
+ * sgdfr_pool_mse_f32: one walk over x (the walk of sgdfr_sweep_frames_f32: pooled [B,3,P,P] has its bits) that also sums
+ *   (pooled - real)^2: per lane over its pixels, per block through the wave sums and LDS into partial[blockIdx.x] of the workspace,
+ *   then one block adds the partials in a fixed order, in double, and writes mse[0] = sum / (3*B*P*P).  No float atomics: the same bits from call
+ *   to call (the 16-byte and the dword walk group the terms differently, so the last bits of mse depend on the path; pooled does
+ *   not).  workspace: sgdfr_pool_mse_workspace_bytes(B, P) bytes (-1 for sizes out of range).
+ * sgdfr_pool_mse_bwd_f32: one launch, dx [B,3,P*f,P*f] = (g_pooled[b,c,Y/f,X/f] + g_mse[0] * 2 (pooled - real) / (3*B*P*P)) / f^2;
+ *   g_pooled [B,3,P,P] and g_mse (a device scalar) may each be NULL (= zeros).  16-byte stores when P*f is a multiple of 4 and dx is
+ *   16-byte aligned, dword stores of the same values otherwise.
+ * No host synchronisation, everything on `stream`. */
+int64_t sgdfr_pool_mse_workspace_bytes(int B, int P);
+int sgdfr_pool_mse_f32(const float* x, const float* real, int B, int P, int f, float* pooled, float* mse, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int sgdfr_pool_mse_bwd_f32(const float* g_pooled, const float* pooled, const float* real, const float* g_mse, int B, int P, int f,
+                           float* dx, void* stream);
+
 /* Rendered rows -> grid video frames in one pass (the frames of a session that pools, reenact.ReenactmentSession(pool_to=...)):
  * x [B,3,P*f,P*f] float32, f = 1, 2 or 4 -> frames [B,P,(n_left+1)*P,3] uint8.  Panels 0 .. n_left-1 (n_left <= 3) are
  * `panels[k]` [B or 1,3,P,P] float32 with batch stride `bstrides[k]` (3*P*P, or 0 = the same image in every frame); both are HOST
@@ -977,7 +995,13 @@ int sgdfr_s3fd_forward_f32(const float* x, int rows, int H, int W, int subtract_
  *   p2 [rows,512,R/8,R/8], p1 [rows,512,R/4,R/4] and the head vectors in front of the EqualLinears [rows,style_count,512].
  * A bad R, rows < 1 or a workspace below sgdfr_e4e_workspace_bytes(rows, R) bytes is an error (the size functions return -1 for
  *   sizes out of range).  The split-K plan follows rows and R only.
- * Deterministic (no float atomics), no host synchronisation, everything on `stream`. */
+ * Deterministic (no float atomics), no host synchronisation, everything on `stream`.
+ * The `_n` entries take the head count `styles` beside the input side: the reference's style_count = 2 log2(image_resolution) - 2
+ *   (psp_encoders.py:143-156), 8..18 for an image_resolution of 32..1024, independent of R (the 512 and 1024 generators' encoders
+ *   read the same 256 x 256 crop and have 16 and 18 heads: heads 0-2 on c3, 3-6 on p2, 7..styles-1 on p1).  R as above.  Every entry
+ *   without `_n` is its `_n` form at styles = sgdfr_e4e_style_count(R); sgdfr_e4e_param_count_n(256, 18) = 423 + 4 * 14.  The
+ *   workspace's two parked head-map buffers hold max(64, 8 (styles - 7)) R^2 floats per row: the layout of styles <= 15 is unchanged.
+ *   The split-K plan follows rows, R and styles only. */
 int sgdfr_e4e_style_count(int R);
 int sgdfr_e4e_param_count(int R);
 int64_t sgdfr_e4e_pack_elems(int R);
@@ -986,6 +1010,13 @@ int64_t sgdfr_e4e_workspace_bytes(int rows, int R);
 int sgdfr_e4e_prepack_f32(const float* const* params, int R, float* pack, void* stream);
 int sgdfr_e4e_forward_f32(const float* x, int rows, int R, const float* pack, float* w, float* debug, void* workspace,
                           int64_t workspace_bytes, void* stream);
+int sgdfr_e4e_param_count_n(int R, int styles);
+int64_t sgdfr_e4e_pack_elems_n(int R, int styles);
+int64_t sgdfr_e4e_debug_elems_n(int rows, int R, int styles);
+int64_t sgdfr_e4e_workspace_bytes_n(int rows, int R, int styles);
+int sgdfr_e4e_prepack_n_f32(const float* const* params, int R, int styles, float* pack, void* stream);
+int sgdfr_e4e_forward_n_f32(const float* x, int rows, int R, int styles, const float* pack, float* w, float* debug, void* workspace,
+                            int64_t workspace_bytes, void* stream);
 
 /* The FFHQ alignment crop in front of the e4e encoder (libs/face_models/ffhq_cropping.py:13-69 crop_using_landmarks with
  * pad_img_to_fit_bbox and crop_from_bbox), csrc/facecrop.hip.  frames [rows,H,W,3] uint8, landmarks [rows,68,2] fp32, both on the

@@ -216,6 +216,9 @@ SIGNATURES['sgdfr_s3fd_forward_f32'] = [_c_f32p, _i, _i, _i, _i, _c_f32p, _f, _i
 S3FD_PARAMS = 50        # pointers sgdfr_s3fd_prepack_f32 takes
 SIGNATURES['sgdfr_e4e_prepack_f32'] = [ctypes.POINTER(ctypes.c_void_p), _i, _c_f32p, ctypes.c_void_p]
 SIGNATURES['sgdfr_e4e_forward_f32'] = [_c_f32p, _i, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+# the `_n` forms take the head count (8..18) beside the input side
+SIGNATURES['sgdfr_e4e_prepack_n_f32'] = [ctypes.POINTER(ctypes.c_void_p), _i, _i, _c_f32p, ctypes.c_void_p]
+SIGNATURES['sgdfr_e4e_forward_n_f32'] = [_c_f32p, _i, _i, _i, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
 _u8p = ctypes.c_void_p                   # uint8_t* on the device
 SIGNATURES['sgdfr_facecrop_boxes_f32'] = [_c_f32p, _i, _ip, _ip, ctypes.c_void_p]
 SIGNATURES['sgdfr_facecrop_forward_u8'] = [_u8p, _c_f32p, _i, _i, _i, _i, _i, _u8p, _ip, _c_f32p, _ip, _ip, _c_f32p, ctypes.c_void_p, _i64,
@@ -240,6 +243,8 @@ SIGNATURES['sgdfr_sweep_rows_f32'] = [ctypes.c_void_p, _ip, ctypes.POINTER(Direc
                                       ctypes.c_void_p]
 SIGNATURES['sgdfr_sweep_rows_host'] = [ctypes.c_void_p, ctypes.POINTER(Direction), _i, _host_ip, _i, _i, _c_f32p, _ip, _ip, _i64]
 SIGNATURES['sgdfr_sweep_frames_f32'] = [_c_f32p, _i, _i, _i, _ip, _c_f32p, _i64, _c_f32p, _c_f32p, _u8p, _i, ctypes.c_void_p]
+SIGNATURES['sgdfr_pool_mse_f32'] = [_c_f32p, _c_f32p, _i, _i, _i, _c_f32p, _c_f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]
+SIGNATURES['sgdfr_pool_mse_bwd_f32'] = [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _i, _i, _i, _c_f32p, ctypes.c_void_p]
 SIGNATURES['sgdfr_video_frames_f32'] = [_c_f32p, _i, _i, _i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), _i, _u8p, _i,
                                         ctypes.c_void_p]
 
@@ -295,6 +300,8 @@ SIZE_QUERIES = {
     'sgdfr_fandepth_pack_elems': 0, 'sgdfr_fandepth_debug_elems': 1, 'sgdfr_fandepth_workspace_bytes': 1,
     'sgdfr_s3fd_pack_elems': 0, 'sgdfr_s3fd_debug_elems': 3, 'sgdfr_s3fd_map_elems': 3, 'sgdfr_s3fd_workspace_bytes': 3,
     'sgdfr_e4e_pack_elems': 1, 'sgdfr_e4e_debug_elems': 2, 'sgdfr_e4e_workspace_bytes': 2,
+    'sgdfr_e4e_pack_elems_n': 2, 'sgdfr_e4e_debug_elems_n': 3, 'sgdfr_e4e_workspace_bytes_n': 3,
+    'sgdfr_pool_mse_workspace_bytes': 2,
     'sgdfr_facecrop_workspace_bytes': 4,
     'sgdfr_pairloss_workspace_bytes': 1,
     'sgdfr_shaperender_workspace_bytes': 3,
@@ -302,6 +309,7 @@ SIZE_QUERIES = {
     'sgdfr_flametex_pack_elems': 2,
 }
 COUNT_QUERIES = ('sgdfr_e4e_style_count', 'sgdfr_e4e_param_count')      # int (int R): a count, or -1 for a resolution out of range
+COUNT_QUERIES_N = {'sgdfr_e4e_param_count_n': 2}                         # int (int R, int styles): the same with the head count given
 
 MODE_PLAIN3, MODE_UP3, MODE_DOWN3 = 0, 1, 2
 SPLIT_BF16, SPLIT_FP16, SPLIT_FP16F8 = 0, 1, 2      # include/sgdfr.h SGDFR_SPLIT_*
@@ -329,6 +337,9 @@ def load():
         getattr(lib, name).restype = ctypes.c_int64
     for name in COUNT_QUERIES:
         getattr(lib, name).argtypes = [ctypes.c_int]
+        getattr(lib, name).restype = ctypes.c_int
+    for name, nargs in COUNT_QUERIES_N.items():
+        getattr(lib, name).argtypes = [ctypes.c_int] * nargs
         getattr(lib, name).restype = ctypes.c_int
     if lib.sgdfr_abi_version() != ABI_VERSION:
         raise RuntimeError('libsgdfr_hip.so ABI %d != expected %d: rebuild' % (lib.sgdfr_abi_version(), ABI_VERSION))

@@ -228,7 +228,9 @@ def _conv_input_grad(mod, g_pre, g_max, d, planes, shape, bw_arith, want_planes_
             gu = F_.modconv_raw(gT, mod.packed_t(), ones_d, None, cin, N.MODE_DOWN3, H, W,
                                 desc='bwd down3 %d->%d @%dx%d' % (cout, cin, H, W))
     else:
-        if F_.split_ok(B, cout, cin, H, W):    # dL/dx of a plain conv is a plain conv: same kernels, adjoint packs.
+        # (cin % 64: split_ok also admits a half cout tile, which only the forward pack pads -- the 32-channel layers of the 512^2 and
+        # 1024^2 generators take the exact kernels below)
+        if cin % 64 == 0 and F_.split_ok(B, cout, cin, H, W):    # dL/dx of a plain conv is a plain conv: same kernels, adjoint packs.
             # Gradients have no natural scale (1e-8 is as likely as 1e+3): the fp16 terms are planned from max |g_pre| of each
             # image (d_in / d_out above), bf16 terms (fp32 range, 2^-17 per product) need no plan.
             gu = F_.modconv_split(g_pre, mod.packed_split(adjoint=True, arith=bw_arith), d_in, d_out, cin,

@@ -1,9 +1,12 @@
 // The e4e W+ encoder in eval mode (libs/gan/encoder4editing/psp_encoders.py:33-53 GradualStyleBlock and :122-199 Encoder4Editing(50,
 // 'ir_se', R), helpers.py:57-140): stem conv3x3 + BN + PReLU at R x R -> 24 bottleneck_IR_SE units (3 x 64, 4 x 128, 14 x 256, 3 x 512
 // channels, the first of a stage at stride 2) with taps c1, c2, c3 behind units 6, 20, 23 -> p2 = bilinear(c3) + latlayer1(c2),
-// p1 = bilinear(p2) + latlayer2(c1) (align_corners=True) -> 2 log2(R) - 2 style heads (heads 0-2 on c3 with 4 convs, 3-6 on p2 with 5,
+// p1 = bilinear(p2) + latlayer2(c1) (align_corners=True) -> `styles` style heads (heads 0-2 on c3 with 4 convs, 3-6 on p2 with 5,
 // 7.. on p1 with 6; conv3x3 stride 2 + bias + LeakyReLU(0.01) down to 1 x 1, then EqualLinear) -> w[:, 0] = w0, w[:, i] = w0 + delta_i.
 // Forward only: every call of the reference is under no_grad.
+// The head count is the reference's style_count = 2 log2(image_resolution) - 2 (psp_encoders.py:143-156), 8..18 for 32..1024, and is
+// independent of the input side R: the 512 and 1024 generators are fed from the same 256 x 256 crop, with 16 and 18 heads.  The
+// entries without `_n` take styles = 2 floor(log2 R) - 2, the encoder whose image_resolution is its input side.
 //
 // Every conv and the head GEMMs are one implicit-GEMM kernel on exact-f32 MFMA (v_mfma_f32_16x16x4_f32), the 64 x 64 x 16 tile with
 // the double-buffered K loop, the split over K and the fixed-order finish of idloss.hip.  BN1 sits in front of a zero-padded conv and
@@ -26,7 +29,8 @@
 namespace sgdfr {
 namespace {
 
-constexpr int kUnits = 24, kMaxHeads = 14, kMaxDepth = 6, kGroups = 3, kStyle = 512;
+constexpr int kUnits = 24, kMinHeads = 8, kMaxHeads = 18, kMaxDepth = 6, kGroups = 3, kStyle = 512;
+constexpr int kParkedHeads = 14;                   // the head vectors' two buffers hold at least this many heads per row
 constexpr int kMinRes = 32, kMaxRes = 256, kMaxRows = 256;
 constexpr int64_t kMaxPixels = 1LL << 24;           // rows * R * R: every element index of a 64-channel map stays below 2^31
 constexpr int kTrunkParams = 3 + 10 * kUnits + 4;   // stem, units, the two lateral convs
@@ -56,6 +60,8 @@ static void make_units(Unit* u, int R) {
         }
 }
 static bool res_ok(int R) { return R >= kMinRes && R <= kMaxRes && R % 16 == 0; }
+static bool styles_ok(int n) { return n >= kMinHeads && n <= kMaxHeads; }
+// rows * R * R <= 2^24 also keeps the widest parked head map, 11 heads x 512 channels at R/8 = 88 R^2 floats per row, below 2^31
 static bool size_ok(int rows, int R) { return res_ok(R) && rows >= 1 && rows <= kMaxRows && (int64_t)rows * R * R <= kMaxPixels; }
 static int style_count(int R) {
     int l = 0;
@@ -65,14 +71,13 @@ static int style_count(int R) {
 struct Group {
     int lo, hi, depth, side;            // heads lo..hi-1 read a [512, side, side] map with `depth` convs
 };
-static void make_groups(Group* g, int R) {
-    const int n = style_count(R);
+static void make_groups(Group* g, int R, int n) {
     g[0] = Group{0, 3, 4, R / 16}, g[1] = Group{3, 7, 5, R / 8}, g[2] = Group{7, n, 6, R / 4};
 }
 static int group_of(int head) { return head < 3 ? 0 : head < 7 ? 1 : 2; }
-static int param_count(int R) {
+static int param_count(int R, int styles) {
     Group g[kGroups];
-    make_groups(g, R);
+    make_groups(g, R, styles);
     int n = kTrunkParams;
     for (int i = 0; i < kGroups; ++i) n += (g[i].hi - g[i].lo) * (2 * g[i].depth + 2);
     return n;
@@ -89,11 +94,11 @@ struct PackLayout {
     int64_t hw[kGroups][kMaxDepth], hb[kGroups][kMaxDepth];   // depth 0: [4608][G*512]; deeper: per head [4608][512]
     int64_t lw, lb, total;                                    // EqualLinear: per head [512][512] (scaled on the host), [512]
 };
-static PackLayout pack_layout(int R) {
+static PackLayout pack_layout(int R, int styles) {
     Unit us[kUnits];
     make_units(us, R);
     Group gs[kGroups];
-    make_groups(gs, R);
+    make_groups(gs, R, styles);
     PackLayout p;
     memset(&p, 0, sizeof(p));
     int64_t o = 0;
@@ -114,7 +119,7 @@ static PackLayout pack_layout(int R) {
         const int G = gs[g].hi - gs[g].lo;
         for (int k = 0; k < gs[g].depth; ++k) p.hw[g][k] = take(9LL * kStyle * kStyle * G), p.hb[g][k] = take((int64_t)kStyle * G);
     }
-    const int n = style_count(R);
+    const int n = styles;
     p.lw = take((int64_t)n * kStyle * kStyle), p.lb = take((int64_t)n * kStyle);
     p.total = o;
     return p;
@@ -378,7 +383,7 @@ static int live_taps(int side, unsigned long long& taps) {
 struct DebugLayout {
     int64_t stem, u0, u3, c1, c2, c3, p2, p1, h, total;
 };
-static DebugLayout debug_layout(int rows, int R) {
+static DebugLayout debug_layout(int rows, int R, int styles) {
     DebugLayout d;
     int64_t o = 0;
     auto take = [&](int64_t n) { const int64_t r = o; o += n; return r; };
@@ -386,7 +391,7 @@ static DebugLayout debug_layout(int rows, int R) {
     d.stem = take(64 * r2), d.u0 = take(64 * r2 / 4), d.u3 = take(128 * r2 / 16);
     d.c1 = take(128 * r2 / 16), d.c2 = take(256 * r2 / 64), d.c3 = take(512 * r2 / 256);
     d.p2 = take(512 * r2 / 64), d.p1 = take(512 * r2 / 16);
-    d.h = take((int64_t)rows * style_count(R) * kStyle);
+    d.h = take((int64_t)rows * styles * kStyle);
     d.total = o;
     return d;
 }
@@ -394,20 +399,25 @@ static DebugLayout debug_layout(int rows, int R) {
 struct WsLayout {
     int64_t part, act[2], p1, c2, mean, gate, t1, t2, t3, f2, f1, h, delta, total;   // float offsets
 };
-static WsLayout ws_layout(int rows, int R) {
+static WsLayout ws_layout(int rows, int R, int styles) {
     WsLayout w;
     int64_t o = 0;
     auto take = [&](int64_t n) { const int64_t r = o; o = align64(o + n); return r; };
     const int64_t r2 = (int64_t)rows * R * R;
     w.part = take(kPartElems);
-    // the two unit buffers and conv1's output hold [64, R, R] per row; behind the trunk the first two hold the head maps
-    // (at most 7 heads x 512 channels at R/8: 56 R^2 per row)
-    w.act[0] = take(64 * r2), w.act[1] = take(64 * r2), w.p1 = take(64 * r2);
+    // the two unit buffers and conv1's output hold [64, R, R] per row; behind the trunk the first two hold the head maps, the
+    // widest of them the fine group's first conv: G heads x 512 channels at R/8 = 8 G R^2 per row.  7 heads (56 R^2) fit the unit
+    // buffer; 9 and 11 heads (72 and 88 R^2) size it
+    Group gs[kGroups];
+    make_groups(gs, R, styles);
+    const int64_t parked = std::max<int64_t>(64 * r2, (int64_t)(gs[2].hi - gs[2].lo) * kStyle * r2 / 64);
+    w.act[0] = take(parked), w.act[1] = take(parked), w.p1 = take(64 * r2);
     w.c2 = take(64 * r2 / 4);
     w.mean = take((int64_t)rows * 512), w.gate = take((int64_t)rows * 512);
     w.t1 = take(128 * r2 / 16), w.t2 = take(256 * r2 / 64), w.t3 = take(512 * r2 / 256);
     w.f2 = take(512 * r2 / 64), w.f1 = take(512 * r2 / 16);
-    w.h = take((int64_t)rows * kMaxHeads * kStyle), w.delta = take((int64_t)rows * kMaxHeads * kStyle);
+    const int held = std::max(styles, kParkedHeads);
+    w.h = take((int64_t)rows * held * kStyle), w.delta = take((int64_t)rows * held * kStyle);
     w.total = o;
     return w;
 }
@@ -419,30 +429,43 @@ using namespace sgdfr;
 
 extern "C" int sgdfr_e4e_style_count(int R) { return res_ok(R) ? style_count(R) : -1; }
 
-extern "C" int sgdfr_e4e_param_count(int R) { return res_ok(R) ? param_count(R) : -1; }
+extern "C" int sgdfr_e4e_param_count_n(int R, int styles) { return res_ok(R) && styles_ok(styles) ? param_count(R, styles) : -1; }
 
-extern "C" int64_t sgdfr_e4e_pack_elems(int R) { return res_ok(R) ? pack_layout(R).total : -1; }
+extern "C" int64_t sgdfr_e4e_pack_elems_n(int R, int styles) { return res_ok(R) && styles_ok(styles) ? pack_layout(R, styles).total : -1; }
 
-extern "C" int64_t sgdfr_e4e_debug_elems(int rows, int R) { return size_ok(rows, R) ? debug_layout(rows, R).total : -1; }
-
-extern "C" int64_t sgdfr_e4e_workspace_bytes(int rows, int R) {
-    return size_ok(rows, R) ? ws_layout(rows, R).total * (int64_t)sizeof(float) : -1;
+extern "C" int64_t sgdfr_e4e_debug_elems_n(int rows, int R, int styles) {
+    return size_ok(rows, R) && styles_ok(styles) ? debug_layout(rows, R, styles).total : -1;
 }
 
-extern "C" int sgdfr_e4e_prepack_f32(const float* const* params, int R, float* pack, void* stream) {
+extern "C" int64_t sgdfr_e4e_workspace_bytes_n(int rows, int R, int styles) {
+    return size_ok(rows, R) && styles_ok(styles) ? ws_layout(rows, R, styles).total * (int64_t)sizeof(float) : -1;
+}
+
+// the entries without `_n`: the head count that follows the input side.  A bad R gets a count in range: the `_n` form refuses the R
+static int own_styles(int R) { return res_ok(R) ? style_count(R) : kMinHeads; }
+extern "C" int sgdfr_e4e_param_count(int R) { return sgdfr_e4e_param_count_n(R, own_styles(R)); }
+
+extern "C" int64_t sgdfr_e4e_pack_elems(int R) { return sgdfr_e4e_pack_elems_n(R, own_styles(R)); }
+
+extern "C" int64_t sgdfr_e4e_debug_elems(int rows, int R) { return sgdfr_e4e_debug_elems_n(rows, R, own_styles(R)); }
+
+extern "C" int64_t sgdfr_e4e_workspace_bytes(int rows, int R) { return sgdfr_e4e_workspace_bytes_n(rows, R, own_styles(R)); }
+
+extern "C" int sgdfr_e4e_prepack_n_f32(const float* const* params, int R, int styles, float* pack, void* stream) {
     SGDFR_REQUIRE(res_ok(R), "e4e_prepack: resolution %d (a multiple of 16 in %d..%d)", R, kMinRes, kMaxRes);
+    SGDFR_REQUIRE(styles_ok(styles), "e4e_prepack: %d style heads (%d..%d)", styles, kMinHeads, kMaxHeads);
     SGDFR_REQUIRE(params && pack, "e4e_prepack: null pointer");
     Unit us[kUnits];
     make_units(us, R);
     Group gs[kGroups];
-    make_groups(gs, R);
-    const int count = param_count(R);
+    make_groups(gs, R, styles);
+    const int count = param_count(R, styles);
     for (int i = 0; i < count; ++i) {
         const int u = (i - 3) / 10, j = (i - 3) % 10;
         const bool optional = i >= 3 && i < 3 + 10 * kUnits && j >= 8 && !us[u].sc_conv;   // shortcut conv of an identity unit
         SGDFR_REQUIRE(optional || params[i], "e4e_prepack: parameter %d is null", i);
     }
-    const PackLayout pl = pack_layout(R);
+    const PackLayout pl = pack_layout(R, styles);
     hipStream_t st = as_stream(stream);
     auto copy = [&](const float* src, int64_t dst, int64_t n) {
         hipLaunchKernelGGL(e4e_pack_kernel, dim3(grid_1d(n)), dim3(kThreads), 0, st, src, pack + dst, n, 1, 0, 0, 0, 0, 0);
@@ -482,7 +505,7 @@ extern "C" int sgdfr_e4e_prepack_f32(const float* const* params, int R, float* p
         rc |= copy(P[3], pl.bl2, kStyle);
     }
     P += 4;
-    const int n = style_count(R);
+    const int n = styles;
     for (int h = 0; h < n && !rc; ++h) {
         const int g = group_of(h), j = h - gs[g].lo, G = gs[g].hi - gs[g].lo;
         // the first conv: this head's 512 columns of the group's [4608][G*512] matrix
@@ -500,21 +523,26 @@ extern "C" int sgdfr_e4e_prepack_f32(const float* const* params, int R, float* p
     return rc ? 2 : 0;
 }
 
-extern "C" int sgdfr_e4e_forward_f32(const float* x, int rows, int R, const float* pack, float* w, float* debug, void* workspace,
-                                     int64_t workspace_bytes, void* stream) {
+extern "C" int sgdfr_e4e_prepack_f32(const float* const* params, int R, float* pack, void* stream) {
+    return sgdfr_e4e_prepack_n_f32(params, R, own_styles(R), pack, stream);
+}
+
+extern "C" int sgdfr_e4e_forward_n_f32(const float* x, int rows, int R, int styles, const float* pack, float* w, float* debug,
+                                       void* workspace, int64_t workspace_bytes, void* stream) {
     SGDFR_REQUIRE(res_ok(R), "e4e_forward: resolution %d (a multiple of 16 in %d..%d, so that every head ends at 1x1)", R, kMinRes, kMaxRes);
+    SGDFR_REQUIRE(styles_ok(styles), "e4e_forward: %d style heads (%d..%d)", styles, kMinHeads, kMaxHeads);
     SGDFR_REQUIRE(size_ok(rows, R), "e4e_forward: %d rows at resolution %d (1..%d rows, rows*R*R <= 2^24)", rows, R, kMaxRows);
     SGDFR_REQUIRE(x && pack && w && workspace, "e4e_forward: null pointer");
-    const WsLayout wl = ws_layout(rows, R);
+    const WsLayout wl = ws_layout(rows, R, styles);
     SGDFR_REQUIRE(wl.total * (int64_t)sizeof(float) <= workspace_bytes, "e4e_forward: workspace of %lld bytes, %d rows at %d need %lld",
                   (long long)workspace_bytes, rows, R, (long long)(wl.total * (int64_t)sizeof(float)));
     Unit us[kUnits];
     make_units(us, R);
     Group gs[kGroups];
-    make_groups(gs, R);
-    const PackLayout pl = pack_layout(R);
-    const DebugLayout dl = debug_layout(rows, R);
-    const int n_styles = style_count(R);
+    make_groups(gs, R, styles);
+    const PackLayout pl = pack_layout(R, styles);
+    const DebugLayout dl = debug_layout(rows, R, styles);
+    const int n_styles = styles;
     float* wsf = reinterpret_cast<float*>(workspace);
     float* part = wsf + wl.part;
     hipStream_t st = as_stream(stream);
@@ -632,4 +660,9 @@ extern "C" int sgdfr_e4e_forward_f32(const float* x, int rows, int R, const floa
     hipLaunchKernelGGL(e4e_wplus_kernel, dim3(grid_1d((int64_t)rows * n_styles * kStyle)), dim3(kThreads), 0, st, wsf + wl.delta, w, rows,
                        n_styles);
     return check_launch("e4e w plus");
+}
+
+extern "C" int sgdfr_e4e_forward_f32(const float* x, int rows, int R, const float* pack, float* w, float* debug, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+    return sgdfr_e4e_forward_n_f32(x, rows, R, own_styles(R), pack, w, debug, workspace, workspace_bytes, stream);
 }

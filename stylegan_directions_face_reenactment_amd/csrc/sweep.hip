@@ -21,6 +21,8 @@
 // host, so sgdfr_sweep_plan_host runs the same function and proves the ladder on a machine without a GPU.
 #include <math.h>
 
+#include <algorithm>
+
 #include "common.h"
 
 namespace sgdfr {
@@ -274,16 +276,18 @@ __device__ __forceinline__ void pooled_walk_scalar(const float* __restrict__ x, 
 
 // The launch of a walk: 16-byte lanes where a row of x is a whole number of them and x starts on one, a grid-stride loop over at
 // most 65536 blocks of kWalkBlock threads (the kernels read it as blockDim.x), the kernel picked by f.  The kernels take (x, R, P, tail...), the dword one (x, R, P, f, tail...).
+constexpr int64_t kWalkMaxBlocks = 65536;
+static bool walk_vec(const void* p, int P, int f) { return (P * f) % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static int64_t walk_blocks(bool vec, int R, int P, int f) {
+    const int64_t items = vec ? (int64_t)R * P * (P * f / 4) : (int64_t)R * P * P;
+    return std::min((items + kWalkBlock - 1) / kWalkBlock, kWalkMaxBlocks);
+}
 template <class... T>
 static void launch_walk(void (*vec1)(const float*, int, int, T...), void (*vec2)(const float*, int, int, T...),
                         void (*vec4)(const float*, int, int, T...), void (*scalar)(const float*, int, int, int, T...), const float* x,
                         int R, int P, int f, void* stream, T... tail) {
-    const int W = P * f;
-    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int64_t items = vec ? (int64_t)R * P * (W / 4) : (int64_t)R * P * P;
-    int64_t blocks = (items + kWalkBlock - 1) / kWalkBlock;
-    if (blocks > 65536) blocks = 65536;
-    const dim3 grid((unsigned)blocks), block(kWalkBlock);
+    const bool vec = walk_vec(x, P, f);
+    const dim3 grid((unsigned)walk_blocks(vec, R, P, f)), block(kWalkBlock);
     hipStream_t st = as_stream(stream);
     if (!vec) hipLaunchKernelGGL(scalar, grid, block, 0, st, x, R, P, f, tail...);
     else hipLaunchKernelGGL(f == 1 ? vec1 : f == 2 ? vec2 : vec4, grid, block, 0, st, x, R, P, tail...);
@@ -298,6 +302,123 @@ __global__ __launch_bounds__(kWalkBlock) void sweep_frames_vec_kernel(const floa
 
 __global__ __launch_bounds__(kWalkBlock) void sweep_frames_scalar_kernel(const float* __restrict__ x, int R, int P, int f, FramesOut o) {
     pooled_walk_scalar(x, R, P, f, blockDim.x, [=](int r, int oy, int ox0, const float (&v)[3][1]) { put_pixels(o, r, oy, ox0, P, v); });
+}
+
+// ---------------------------------------------------------------- pooled image loss
+// PTI above 256^2 compares the pooled image with the crop: the walk into the pooled floats and sum (pooled - real)^2, and the
+// gradient of both back onto the unpooled image.  The sum has no float atomics: a lane adds its pixels in walk order, a block its
+// lanes (wave_sum, then the four wave totals in wave order) into partial[blockIdx.x], one block the partials (lane t the partials
+// t, t + 256, ... in double, then a pairwise tree over the lanes).  The grid follows the shape and the path alone, so mse has the same bits every call.
+static_assert(kWalkBlock == 4 * kWave, "block_sum adds four wave totals");
+
+// the sum over the block's 256 lanes, in every lane.  All lanes call it, behind their loops (wave_sum's precondition)
+__device__ __forceinline__ float block_sum(float v, float (&sh)[4]) {
+    v = wave_sum(v);
+    if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+struct PoolMseOut {
+    float* pooled;
+    const float* real;
+    float* partial;
+};
+
+template <int NPIX>
+__device__ __forceinline__ void pool_mse_pixels(const PoolMseOut& o, int r, int oy, int ox0, int P, const float (&v)[3][NPIX], float& acc) {
+    const int64_t PP = (int64_t)P * P;
+    const int64_t at = (int64_t)r * 3 * PP + (int64_t)oy * P + ox0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int p = 0; p < NPIX; ++p) {
+            o.pooled[at + c * PP + p] = v[c][p];
+            const float d = v[c][p] - o.real[at + c * PP + p];
+            acc = fmaf(d, d, acc);
+        }
+}
+
+template <int F>
+__global__ __launch_bounds__(kWalkBlock) void pool_mse_vec_kernel(const float* __restrict__ x, int R, int P, PoolMseOut o) {
+    __shared__ float sh[4];
+    float acc = 0.f;
+    pooled_walk_vec<F>(x, R, P, blockDim.x, [=, &acc](int r, int oy, int ox0, const float (&v)[3][4 / F]) { pool_mse_pixels(o, r, oy, ox0, P, v, acc); });
+    const float s = block_sum(acc, sh);
+    if (threadIdx.x == 0) o.partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kWalkBlock) void pool_mse_scalar_kernel(const float* __restrict__ x, int R, int P, int f, PoolMseOut o) {
+    __shared__ float sh[4];
+    float acc = 0.f;
+    pooled_walk_scalar(x, R, P, f, blockDim.x, [=, &acc](int r, int oy, int ox0, const float (&v)[3][1]) { pool_mse_pixels(o, r, oy, ox0, P, v, acc); });
+    const float s = block_sum(acc, sh);
+    if (threadIdx.x == 0) o.partial[blockIdx.x] = s;
+}
+
+// the partials in index order per lane, then a pairwise tree over the lanes; in double, rounded once, behind the division
+__global__ __launch_bounds__(kWalkBlock) void pool_mse_finish_kernel(const float* __restrict__ partial, int n, double count, float* __restrict__ mse) {
+    __shared__ double sh[kWalkBlock];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += kWalkBlock) s += (double)partial[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kWalkBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) mse[0] = (float)(sh[0] / count);
+}
+
+// d(loss)/d(x) at every input pixel under output pixel `at`: one rounding per operation in both store paths, so they agree bit for bit
+struct PoolMseGrad {
+    const float* g_pooled;
+    const float* pooled;
+    const float* real;
+    const float* g_mse;
+    float count, ff;
+};
+__device__ __forceinline__ float pool_mse_grad(const PoolMseGrad& g, float gm, int64_t at) {
+    const float gp = g.g_pooled ? g.g_pooled[at] : 0.f;
+    const float k = g.g_mse ? __fdiv_rn(__fmul_rn(2.f, __fsub_rn(g.pooled[at], g.real[at])), g.count) : 0.f;
+    return __fdiv_rn(fmaf(gm, k, gp), g.ff);
+}
+
+// 16-byte path: a lane stores four consecutive columns of one row of dx = 4 / F output pixels' values
+template <int F>
+__global__ __launch_bounds__(kWalkBlock) void pool_mse_bwd_vec_kernel(PoolMseGrad g, int B, int P, float* __restrict__ dx) {
+    const int W = P * F, Q = W / 4;
+    const int64_t items = (int64_t)B * 3 * W * Q;
+    const float gm = g.g_mse ? g.g_mse[0] : 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % Q);
+        const int64_t t = i / Q;
+        const int Y = (int)(t % W);
+        const int64_t bc = t / W;
+        const int64_t at = (bc * P + Y / F) * P + (q * 4) / F;
+        float v[4];
+#pragma unroll
+        for (int p = 0; p < 4 / F; ++p) {
+            const float e = pool_mse_grad(g, gm, at + p);
+#pragma unroll
+            for (int j = 0; j < F; ++j) v[p * F + j] = e;
+        }
+        *reinterpret_cast<float4*>(dx + (bc * W + Y) * W + (int64_t)q * 4) = float4{v[0], v[1], v[2], v[3]};
+    }
+}
+
+// dword path: one element of dx per lane
+__global__ __launch_bounds__(kWalkBlock) void pool_mse_bwd_scalar_kernel(PoolMseGrad g, int B, int P, int f, float* __restrict__ dx) {
+    const int W = P * f;
+    const int64_t items = (int64_t)B * 3 * W * W;
+    const float gm = g.g_mse ? g.g_mse[0] : 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        const int X = (int)(i % W);
+        const int64_t t = i / W;
+        const int Y = (int)(t % W);
+        const int64_t bc = t / W;
+        dx[i] = pool_mse_grad(g, gm, (bc * P + Y / f) * P + X / f);
+    }
 }
 
 // ---------------------------------------------------------------- video frames
@@ -507,6 +628,49 @@ extern "C" int sgdfr_sweep_frames_f32(const float* x, int R, int P, int f, const
     FramesOut o{pooled, bordered, frames, src, src_bstride, is_start, panels};
     launch_walk(SGDFR_WALK_KERNELS(sweep_frames), x, R, P, f, stream, o);
     return check_launch("sweep_frames");
+}
+
+constexpr int kPoolMseMaxRows = 4096;
+static bool pool_mse_ok(int B, int P) { return B >= 1 && B <= kPoolMseMaxRows && P >= 1 && P <= 8192; }
+// one float per block of the widest walk, the dword one: B * P * P items
+static int64_t pool_mse_partials(int B, int P) { return walk_blocks(false, B, P, 1); }
+
+extern "C" int64_t sgdfr_pool_mse_workspace_bytes(int B, int P) {
+    return pool_mse_ok(B, P) ? pool_mse_partials(B, P) * (int64_t)sizeof(float) : -1;
+}
+
+extern "C" int sgdfr_pool_mse_f32(const float* x, const float* real, int B, int P, int f, float* pooled, float* mse, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+    SGDFR_REQUIRE(f == 1 || f == 2 || f == 4, "pool_mse: the pooling factor must be 1, 2 or 4 (256, 512, 1024 generators), got %d", f);
+    SGDFR_REQUIRE(pool_mse_ok(B, P), "pool_mse: bad shape B=%d P=%d (1..%d rows, P in 1..8192)", B, P, kPoolMseMaxRows);
+    SGDFR_REQUIRE(x && real && pooled && mse && workspace, "pool_mse: null pointer");
+    SGDFR_REQUIRE(workspace_bytes >= pool_mse_partials(B, P) * (int64_t)sizeof(float), "pool_mse: workspace of %lld bytes, B=%d P=%d need %lld",
+                  (long long)workspace_bytes, B, P, (long long)(pool_mse_partials(B, P) * (int64_t)sizeof(float)));
+    PoolMseOut o{pooled, real, reinterpret_cast<float*>(workspace)};
+    const int blocks = (int)walk_blocks(walk_vec(x, P, f), B, P, f);       // the grid launch_walk gives the walk
+    launch_walk(SGDFR_WALK_KERNELS(pool_mse), x, B, P, f, stream, o);
+    if (check_launch("pool_mse")) return 2;
+    hipLaunchKernelGGL(pool_mse_finish_kernel, dim3(1), dim3(kWalkBlock), 0, as_stream(stream), (const float*)o.partial, blocks,
+                       3.0 * B * P * P, mse);
+    return check_launch("pool_mse finish");
+}
+
+extern "C" int sgdfr_pool_mse_bwd_f32(const float* g_pooled, const float* pooled, const float* real, const float* g_mse, int B, int P,
+                                      int f, float* dx, void* stream) {
+    SGDFR_REQUIRE(f == 1 || f == 2 || f == 4, "pool_mse_bwd: the pooling factor must be 1, 2 or 4 (256, 512, 1024 generators), got %d", f);
+    SGDFR_REQUIRE(pool_mse_ok(B, P), "pool_mse_bwd: bad shape B=%d P=%d (1..%d rows, P in 1..8192)", B, P, kPoolMseMaxRows);
+    SGDFR_REQUIRE(dx && (!g_mse || (pooled && real)), "pool_mse_bwd: null pointer");
+    const PoolMseGrad g{g_pooled, pooled, real, g_mse, (float)(3.0 * B * P * P), (float)(f * f)};
+    const int W = P * f;
+    const bool vec = walk_vec(dx, P, f);
+    const int64_t items = (int64_t)B * 3 * W * (vec ? W / 4 : W);
+    const dim3 grid((unsigned)std::min((items + kWalkBlock - 1) / kWalkBlock, kWalkMaxBlocks)), block(kWalkBlock);
+    hipStream_t st = as_stream(stream);
+    if (!vec) hipLaunchKernelGGL(pool_mse_bwd_scalar_kernel, grid, block, 0, st, g, B, P, f, dx);
+    else if (f == 1) hipLaunchKernelGGL(pool_mse_bwd_vec_kernel<1>, grid, block, 0, st, g, B, P, dx);
+    else if (f == 2) hipLaunchKernelGGL(pool_mse_bwd_vec_kernel<2>, grid, block, 0, st, g, B, P, dx);
+    else hipLaunchKernelGGL(pool_mse_bwd_vec_kernel<4>, grid, block, 0, st, g, B, P, dx);
+    return check_launch("pool_mse_bwd");
 }
 
 // the float panels of this entry as the tables of the next: stride 0 is a table of one row, stride 3 * P * P one of B rows

@@ -20,6 +20,11 @@ specific to this build:
 
 Beside that, `encode(enc, images)` runs the whole encoder on the hand-written kernels of csrc/e4e.hip (exact-f32 MFMA implicit
 GEMM, forward only, one stream, no host synchronisation); `Encoder4Editing.forward` itself stays on the MIOpen plan.
+
+`image_resolution` and the side of the input are two numbers (psp_encoders.py:143-156, 171-199): the first only sets
+`style_count` = 2 log2(image_resolution) - 2 (14, 16, 18 heads for the 256, 512, 1024 generators), the input is the 256 x 256
+alignment crop for all three.  `input_size` is the side the HIP path is built for; its default min(image_resolution, 256) is the
+old meaning of every construction up to 256.
 """
 import math
 from collections import OrderedDict
@@ -97,18 +102,20 @@ def _fold(conv, bn):
 
 
 class Encoder4Editing(PackedWeights, nn.Module):
-    PREPACK, PACK_ELEMS = 'sgdfr_e4e_prepack_f32', 'sgdfr_e4e_pack_elems'
+    PREPACK, PACK_ELEMS = 'sgdfr_e4e_prepack_n_f32', 'sgdfr_e4e_pack_elems_n'
     TRAIN_ERROR = 'encode: the module is in train() mode; the HIP path folds the BatchNorm statistics, call .eval() first'
     # no GRAD_ERROR: the module's own forward trains; encode() is forward only and returns no graph
     WRAP_STATE_DICT = False         # a checkpoint's `_metadata` decides how its BatchNorms load: the dict is passed on as it comes
 
-    def __init__(self, num_layers, mode='ir', image_resolution=256):
+    def __init__(self, num_layers, mode='ir', image_resolution=256, input_size=None):
         super().__init__()
         if num_layers not in _TRUNK:
             raise ValueError('num_layers should be 50, 100 or 152, got %r' % (num_layers,))
         if mode not in ('ir', 'ir_se'):
             raise ValueError("mode should be 'ir' or 'ir_se', got %r" % (mode,))
         self.num_layers, self.mode, self.image_resolution = num_layers, mode, image_resolution
+        # the side encode() takes: the reference feeds every encoder the 256 x 256 crop, whatever the generator renders
+        self.input_size = min(image_resolution, 256) if input_size is None else input_size
         self.input_layer = nn.Sequential(nn.Conv2d(3, 64, 3, 1, 1, bias=False), nn.BatchNorm2d(64), nn.PReLU(64))
         units, c = [], 64
         for depth, n in _TRUNK[num_layers]:
@@ -176,12 +183,11 @@ class Encoder4Editing(PackedWeights, nn.Module):
         return folded(self, dtype)
 
     def _prepack_plan(self, ps):
-        R, lib = self.image_resolution, N.load()
-        count = lib.sgdfr_e4e_param_count(R)
-        if count != len(ps) or lib.sgdfr_e4e_style_count(R) != self.style_count:
-            raise RuntimeError('encode: %d folded tensors and %d heads, the kernels expect %d and %d at resolution %d' % (
-                len(ps), self.style_count, count, lib.sgdfr_e4e_style_count(R), R))
-        return count, (R,), (R,)
+        R, n, lib = self.input_size, self.style_count, N.load()
+        count = lib.sgdfr_e4e_param_count_n(R, n)
+        if count != len(ps):
+            raise RuntimeError('encode: %d folded tensors, the kernels expect %d for %d heads at an input of %d' % (len(ps), count, n, R))
+        return count, (R, n), (R, n)
 
     def _build_plan(self):
         cl = torch.channels_last
@@ -277,7 +283,7 @@ def _fold64(conv, bn):
 
 
 def folded(enc, dtype=torch.float32):
-    """The tensors sgdfr_e4e_prepack_f32 takes, in the order include/sgdfr.h documents, every BatchNorm but BN1 folded into its
+    """The tensors sgdfr_e4e_prepack_n_f32 takes, in the order include/sgdfr.h documents, every BatchNorm but BN1 folded into its
     conv in fp64 (BN1 sits in front of a zero-padded conv: it travels as scale and shift).  None where a unit has no shortcut conv."""
     out = list(_fold64(enc.input_layer[0], enc.input_layer[1])) + [enc.input_layer[2].weight.detach().double()]
     for unit in enc.body:
@@ -309,19 +315,23 @@ def _check_module(enc):
         raise ValueError("encode: the HIP path runs Encoder4Editing(50, 'ir_se', R) only, got (%r, %r); use the module's own "
                          'forward for the other trunks' % (enc.num_layers, enc.mode))
     enc.check()
-    R = enc.image_resolution
-    if not isinstance(R, int) or R % 16 or not 32 <= R <= 256:
-        raise ValueError('encode: resolution %r is not a multiple of 16 in 32..256 (every style head must end at 1x1)' % (R,))
+    R = getattr(enc, 'input_size', enc.image_resolution)        # (a module unpickled from before input_size existed)
+    if not isinstance(R, int) or isinstance(R, bool) or R % 16 or not 32 <= R <= 256:
+        raise ValueError('encode: input size %r is not a multiple of 16 in 32..256 (every style head must end at 1x1)' % (R,))
+    n = enc.style_count
+    if not isinstance(n, int) or not 8 <= n <= 18 or len(enc.styles) != n:
+        raise ValueError('encode: %r style heads (image_resolution %r), the kernels take 8..18 (image_resolution 32..1024)'
+                         % (n, enc.image_resolution))
     return R
 
 
 def packed(enc):
-    """The device weight pack of sgdfr_e4e_prepack_f32, rebuilt when any parameter's or buffer's storage or version changes."""
+    """The device weight pack of sgdfr_e4e_prepack_n_f32, rebuilt when any parameter's or buffer's storage or version changes."""
     return enc.packed()
 
 
-def _workspace(rows, R, device):
-    return N.workspace('sgdfr_e4e_workspace_bytes', device, rows, R,
+def _workspace(rows, R, style_count, device):
+    return N.workspace('sgdfr_e4e_workspace_bytes_n', device, rows, R, style_count,
                        error='encode: unsupported batch of %d images at resolution %d (1..256 rows, rows*R*R <= 2^24)' % (rows, R))
 
 
@@ -345,21 +355,24 @@ def _encode(enc, images, debug):
         raise ValueError('encode: expected [B,3,%d,%d] images, got %s' % (R, R, tuple(images.shape) if torch.is_tensor(images) else
                                                                          type(images)))
     if images.shape[2] != R or images.shape[3] != R:
-        raise ValueError('encode: images of %dx%d, the module was built for %dx%d' % (images.shape[2], images.shape[3], R, R))
+        raise ValueError('encode: images of %dx%d, the module was built for %dx%d (its input_size: a multiple of 16 in 32..256, '
+                         'whatever image_resolution the heads are counted from)' % (images.shape[2], images.shape[3], R, R))
     N.require_device(images)
     x = N.f32c(images.detach())
     B = x.shape[0]
     lib = N.load()
-    ws, nbytes = _workspace(B, R, x.device)
-    w = torch.empty((B, enc.style_count, 512), dtype=torch.float32, device=x.device)
-    dbg = torch.empty(lib.sgdfr_e4e_debug_elems(B, R), dtype=torch.float32, device=x.device) if debug else None
-    N.call('sgdfr_e4e_forward_f32', N.ptr(x), B, R, N.ptr(packed(enc)), N.ptr(w), N.ptr(dbg), N.ptr(ws), nbytes, N.stream())
-    return w, (None if dbg is None else debug_views(dbg, B, R, enc.style_count))
+    n = enc.style_count
+    ws, nbytes = _workspace(B, R, n, x.device)
+    w = torch.empty((B, n, 512), dtype=torch.float32, device=x.device)
+    dbg = torch.empty(lib.sgdfr_e4e_debug_elems_n(B, R, n), dtype=torch.float32, device=x.device) if debug else None
+    N.call('sgdfr_e4e_forward_n_f32', N.ptr(x), B, R, n, N.ptr(packed(enc)), N.ptr(w), N.ptr(dbg), N.ptr(ws), nbytes, N.stream())
+    return w, (None if dbg is None else debug_views(dbg, B, R, n))
 
 
 def encode(enc, images):
-    """Encoder4Editing(50, 'ir_se', R) on the kernels of csrc/e4e.hip: images [B,3,R,R] float32 in [-1,1] on the device -> W+
-    [B,style_count,512].  Forward only (the result carries no graph), eval mode only, no CPU path, no host synchronisation."""
+    """Encoder4Editing(50, 'ir_se', image_resolution, input_size=R) on the kernels of csrc/e4e.hip: images [B,3,R,R] float32 in
+    [-1,1] on the device, R = enc.input_size -> W+ [B,style_count,512] with style_count = 2 log2(image_resolution) - 2.  Forward
+    only (the result carries no graph), eval mode only, no CPU path, no host synchronisation."""
     return _encode(enc, images, False)[0]
 
 

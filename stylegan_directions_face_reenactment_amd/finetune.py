@@ -1,6 +1,7 @@
 """Generator fine-tuning on one source (PTI), the counterpart of libs/optimization.py:25-72 (`optimize_g`): same parameter
 selection, optimiser and truncation.  The default loss is the L2 term alone (l2_loss_fn); PtiLoss is the reference's
-100 * MSE + LPIPS(alex) on the HIP LPIPS (lpips.py), its target features cached once per source.  The step -- forward, backward through autograd.SynthesisFn, Adam -- can be captured once and
+100 * MSE + LPIPS(alex) on the HIP LPIPS (lpips.py), its target features cached once per source; PooledPtiLoss is the same loss on
+the generator's output pooled to the crop's side, for the 512 and 1024 generators (pool_loss.py).  The step -- forward, backward through autograd.SynthesisFn, Adam -- can be captured once and
 replayed as a hipGraph: at one source per step the eager step is bound by its host launches (~5 ms), the replay takes
 3.4-3.8 ms (bench.py --config pti, scripts/pti_step_bench.py)."""
 import torch
@@ -45,6 +46,40 @@ class PtiLoss:
             self._check(real_imgs)
         loss = torch.nn.functional.mse_loss(imgs_gen, real_imgs) * pt_l2_lambda
         return loss + self.lpips(imgs_gen, self.target) * self.pt_lpips_lambda
+
+
+class PooledPtiLoss:
+    """PtiLoss for a generator above 256^2: the image the loss sees is the one generic.generate_image hands out, the generator's
+    output pooled to P x P (AdaptiveAvgPool2d((256,256)), generic.py:146-148): pt_l2_lambda * mse(pooled, real) + pt_lpips_lambda *
+    LPIPS(pooled, real), pooled and mse from ONE walk over the generated image (pool_loss.PoolMse), whose backward puts both
+    gradients back onto it in one launch.  The reference's optimize_g hands the loss the generator's own 1024^2 output beside the
+    256^2 crop (optimization.py:50-58) and cannot run there.  PtiLoss's contract: real_imgs [B,3,P,P], its LPIPS features cached
+    here, the same-image check in eager mode, callable as optimize_g's loss_fn."""
+
+    def __init__(self, lpips, real_imgs, P=256, pt_lpips_lambda=1.0):
+        if isinstance(P, bool) or not isinstance(P, int) or P < 1:
+            raise ValueError('PooledPtiLoss: P must be a positive int, got %r' % (P,))
+        if not torch.is_tensor(real_imgs) or real_imgs.dim() != 4 or tuple(real_imgs.shape[1:]) != (3, P, P):
+            raise ValueError('PooledPtiLoss: the real images must be [B,3,%d,%d], got %s' % (
+                P, P, tuple(real_imgs.shape) if torch.is_tensor(real_imgs) else type(real_imgs).__name__))
+        self.lpips, self.P = lpips, P
+        self.pt_lpips_lambda = float(pt_lpips_lambda)
+        self.real = real_imgs.detach()
+        self.target = lpips.target(self.real)
+
+    def _check(self, real_imgs):
+        r = self.real
+        if real_imgs.data_ptr() != r.data_ptr() or real_imgs.shape != r.shape or real_imgs.stride() != r.stride():
+            raise RuntimeError('PooledPtiLoss: called with a different real image than it was built for')
+        if real_imgs._version != self.target.source_version:
+            raise RuntimeError('PooledPtiLoss: the real image was modified in place after its LPIPS features were cached')
+
+    def __call__(self, imgs_gen, real_imgs, pt_l2_lambda):
+        from .pool_loss import PoolMse
+        if not (imgs_gen.is_cuda and torch.cuda.is_current_stream_capturing()):      # (a host tensor is refused below, unlaunched)
+            self._check(real_imgs)
+        pooled, mse = PoolMse.apply(imgs_gen, self.real, self.P)
+        return mse * pt_l2_lambda + self.lpips(pooled, self.target) * self.pt_lpips_lambda
 
 
 class FusedAdam:

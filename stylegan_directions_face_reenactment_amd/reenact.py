@@ -724,13 +724,17 @@ class Reenactor:
         videos, ok, sv = r.reenact_many(srcs, a)          # [S,N,256,768,3] uint8; each row what use_source + reenact_analysed gives
         csim, pose, exp_error, ok_r = r.cross_metrics(srcs, a, sv, id_loss)      # [S,N] each
 
-    Three deliberate deviations from the reference:
+    Four deliberate deviations from the reference:
       * a target frame that fails (no face on the frame, an invalid crop, no face on the crop, or the caller's `valid` mask) is
         rendered by a stated policy (`on_fail`); the reference exits on the first two and renders from angles of -180 and zero
         coefficients on the third (estimate_DECA.py:48-51);
       * PTI uses the `trunc` given here; the reference's optimize_g draws a fresh mean_latent(4096) of its own (optimization.py:26);
       * PTI tunes a deep copy: `G` stays bit-unchanged, so the next set_source starts from the base generator.  The reference's
-        optimize_g trains the generator it is handed (optimization.py:28-29 copies it for the regulariser only)."""
+        optimize_g trains the generator it is handed (optimization.py:28-29 copies it for the regulariser only);
+      * PTI on a 512 or 1024 generator compares the output pooled to 256 x 256 with the crop (finetune.PooledPtiLoss): the image
+        generic.generate_image hands out, AdaptiveAvgPool2d((256,256)) of the generator's (generic.py:146-148).  The reference's
+        optimize_g calls the generator directly and hands its loss the 1024^2 output beside the 256^2 crop (optimization.py:50-58):
+        it cannot run there.  `Source.inverted` stays at the generator's own size."""
 
     def __init__(self, G, A, enc, det, fan, E, shifts, truncation=0.7, trunc=None, lpips=None, batch=32):
         if truncation < 1 and trunc is None:
@@ -746,7 +750,8 @@ class Reenactor:
 
     def make_source(self, frame, optimize=True, opt_steps=200, lr=3e-3):
         """Everything `set_source` does short of selecting the source, for one source frame [H,W,3] or [1,H,W,3] uint8 on the device:
-        preprocess_frames at B=1 -> invert_images -> (optimize) finetune.optimize_g with PtiLoss(lpips, x) on a deep copy of G,
+        preprocess_frames at B=1 -> invert_images -> (optimize) finetune.optimize_g with PtiLoss(lpips, x) (a 512 or 1024 generator:
+        PooledPtiLoss(lpips, x, 256), the class docstring's fourth deviation) on a deep copy of G,
         optimize_all=False, the Reenactor's trunc (on G itself without optimisation, run_inference.py:121-124) ->
         train_step.shape_params of the crop x (the cropped real image, not the inversion).  Returns a `Source`; the Reenactor's
         current source and hold carry are untouched, so any number can be made and kept side by side (reenact_many).
@@ -763,9 +768,9 @@ class Reenactor:
             frame = frame.unsqueeze(0)
         if frame.ndim != 4 or frame.shape[0] != 1:
             raise RuntimeError('set_source: one source frame [H,W,3] or [1,H,W,3], got %s' % (tuple(frame.shape),))
-        if optimize and self.G.size != 256:
-            raise RuntimeError('set_source(optimize=True): PTI compares the generator output with the 256 x 256 crop; this generator '
-                               'renders %d x %d' % (self.G.size, self.G.size))
+        if optimize and self.G.size not in (256, 512, 1024):
+            raise RuntimeError('set_source(optimize=True): PTI compares the generator output, pooled by 1, 2 or 4, with the 256 x 256 '
+                               'crop; this generator renders %d x %d' % (self.G.size, self.G.size))
         crop, x, ok = preprocess_frames(self.det, self.fan, frame.contiguous())
         if not bool(ok.item()):                                            # the one host read
             raise RuntimeError('set_source: no usable face in the source frame (no detection, or a crop outside the size limits)')
@@ -776,8 +781,10 @@ class Reenactor:
             import copy
             G_source = copy.deepcopy(self.G)                               # (model.Generator.__deepcopy__ leaves graphs and tokens behind)
             G_source.invalidate_packs()                                    # ... and the copied weight packs are keyed on G's storage
+            # above 256 the loss sees what generate_image hands out: the output pooled to the crop's side (the fourth deviation)
+            loss_fn = finetune.PtiLoss(self.lpips, x) if self.G.size == 256 else finetune.PooledPtiLoss(self.lpips, x, 256)
             G_source, loss = finetune.optimize_g(G_source, code, x, self.trunc, opt_steps=opt_steps, lr=lr, optimize_all=False,
-                                                 loss_fn=finetune.PtiLoss(self.lpips, x), truncation=self.truncation)
+                                                 loss_fn=loss_fn, truncation=self.truncation)
             G_source.eval()
             for p in G_source.parameters():
                 p.grad = None
