@@ -358,7 +358,9 @@ class ToRGB(nn.Module):
 
 
 class Generator(RangePlanMixin, GraphReplayMixin, PlannerMixin, nn.Module):
-    def __init__(self, size, style_dim, n_mlp, channel_multiplier=2, blur_kernel=[1, 3, 3, 1], lr_mlp=0.01):
+    def __init__(self, size, style_dim, n_mlp, channel_multiplier=2, blur_kernel=[1, 3, 3, 1], lr_mlp=0.01, *, channels=None):
+        """channels (keyword only): {resolution: channel count} for every resolution 4, 8, ... size, in place of the reference's
+        table (model.py:389-399) -- generators of other widths with the same modules and state_dict keys; None keeps the table."""
         super().__init__()
         self.size = size
         self.style_dim = style_dim
@@ -366,11 +368,26 @@ class Generator(RangePlanMixin, GraphReplayMixin, PlannerMixin, nn.Module):
         self.style = nn.Sequential(
             PixelNorm(), *[EqualLinear(style_dim, style_dim, lr_mul=lr_mlp, activation='fused_lrelu')
                            for _ in range(n_mlp)])
-        self.channels = {
-            4: 512, 8: 512, 16: 512, 32: 512,
-            64: 256 * channel_multiplier, 128: 128 * channel_multiplier, 256: 64 * channel_multiplier,
-            512: 32 * channel_multiplier, 1024: 16 * channel_multiplier,
-        }
+        if channels is None:
+            self.channels = {
+                4: 512, 8: 512, 16: 512, 32: 512,
+                64: 256 * channel_multiplier, 128: 128 * channel_multiplier, 256: 64 * channel_multiplier,
+                512: 32 * channel_multiplier, 1024: 16 * channel_multiplier,
+            }
+        else:
+            if not isinstance(size, int) or size < 4 or size & (size - 1):
+                raise ValueError('Generator: size must be a power of two >= 4 to take a channels table, got %r' % (size,))
+            if not isinstance(channels, dict):
+                raise TypeError('Generator: channels must be a dict {resolution: channel count}, got %s' % type(channels).__name__)
+            need = [2 ** i for i in range(2, int(math.log(size, 2)) + 1)]
+            missing = [r for r in need if r not in channels]
+            if missing:
+                raise ValueError('Generator: channels has no entry for resolution(s) %s (every one of %s is needed)' % (missing, need))
+            for r in need:
+                c = channels[r]
+                if isinstance(c, bool) or not isinstance(c, int) or c < 1:
+                    raise ValueError('Generator: channels[%d] must be a positive int, got %r' % (r, c))
+            self.channels = {r: channels[r] for r in need}
         self.input = ConstantInput(self.channels[4])
         self.conv1 = StyledConv(self.channels[4], self.channels[4], 3, style_dim, blur_kernel=blur_kernel)
         self.to_rgb1 = ToRGB(self.channels[4], style_dim, upsample=False)
