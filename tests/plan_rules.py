@@ -3,7 +3,9 @@ which convs a forward pass launches at a given size, and into how many K slices 
 slices runs its epilogue in the finish kernel, one with S = 1 ("whole") in the conv kernel itself, so the number of finish launches
 of a pass is the number of launches with S > 1.  tests/test_cpu_e4e_taps.py and tests/test_cpu_s3fd.py pin the geometry to the C
 ABI and assert the coverage condition over the cases listed here; tests/test_gpu_s3fd_e4e_plans.py runs those cases and compares
-the profiler's launch counts with `e4e_counts` / `s3fd_counts`."""
+the profiler's launch counts with `e4e_counts` / `s3fd_counts`.  `detail_plan` is the same for the one layer kernel of csrc/detail.hip
+(sgdfr_detail_upconv_f32): tests/test_cpu_render_seams.py proves what the cases of tests/render_seam_cases.py reach,
+tests/test_gpu_render_seams.py runs them."""
 from collections import OrderedDict, namedtuple
 
 Launch = namedtuple('Launch', 'cls name G N Ho Wo K')
@@ -198,6 +200,70 @@ S3FD_CASES = OrderedDict([
     ('b65', (65, 128, 128, False, (101, 153, 203))),
     ('b240', (240, 32, 320, False, (2, 3))),
 ])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the detail layer
+DetailPlan = namedtuple('DetailPlan', 'bn Ho Wo M K mt nt chunks asked cps S last ktail')
+
+
+def detail_plan(rows, cin, cout, h, w, up):
+    """launch_conv of csrc/detail.hip for sgdfr_detail_upconv_f32: tile 16 for Cout <= 16, else 64; plan_conv of conv_tile.h on the
+    launch's own tiles: at most 512 / tiles slices of at least 8 chunks, at most 32.  `asked` is the slice count the rule asks for,
+    S the one it ends with after the chunks per slice are rounded up; `last` the chunks of the last slice, `ktail` the live K rows
+    of the last chunk (0: it is full)."""
+    f = 2 if up else 1
+    Ho, Wo, K = f * h, f * w, 9 * cin
+    bn = 16 if cout <= 16 else 64
+    M = rows * Ho * Wo
+    mt, nt = _ceil(M, 64), _ceil(cout, bn)
+    chunks = _ceil(K, 16)
+    asked = max(1, min(512 // max(mt * nt, 1), chunks // 8, 32))
+    cps = _ceil(chunks, asked)
+    S = _ceil(chunks, cps)
+    return DetailPlan(bn, Ho, Wo, M, K, mt, nt, chunks, asked, cps, S, chunks - (S - 1) * cps, K % 16)
+
+
+def detail_counts(rows, cin, cout, h, w, up):
+    """(conv launches, finish launches) of one sgdfr_detail_upconv_f32 call."""
+    return 1, int(detail_plan(rows, cin, cout, h, w, up).S > 1)
+
+
+DETAIL_SEAMS = ('uneven_last_slice', 'fewer_slices_than_asked', 'cap_32', 'k_tail_sliced', 'partial_last_channel_tile', 'tile_over_rows',
+                'source_side_1')
+
+
+def detail_seams(rows, cin, cout, h, w, up):
+    """Which of DETAIL_SEAMS one launch reaches.  partial_last_channel_tile: a second (or later) channel tile that is partly empty;
+    tile_over_rows: some 64-pixel tile holds pixels of two or more rows of the batch; source_side_1 is reported per axis as
+    'source_h_1' / 'source_w_1' (the class asks for both over the list)."""
+    p = detail_plan(rows, cin, cout, h, w, up)
+    HWo = p.Ho * p.Wo
+    out = set()
+    if p.S > 1 and p.last != p.cps:
+        out.add('uneven_last_slice')
+    if p.S < p.asked:
+        out.add('fewer_slices_than_asked')
+    if p.S == 32 and min(512 // (p.mt * p.nt), p.chunks // 8) > 32:
+        out.add('cap_32')
+    if p.S > 1 and p.ktail:
+        out.add('k_tail_sliced')
+    if p.nt > 1 and cout % p.bn:
+        out.add('partial_last_channel_tile')
+    if any(m0 // HWo != min(m0 + 63, p.M - 1) // HWo for m0 in range(0, p.M, 64)):
+        out.add('tile_over_rows')
+    if h == 1:
+        out.add('source_h_1')
+    if w == 1:
+        out.add('source_w_1')
+    return out
+
+
+def detail_class(rows, cin, cout, h, w, up):
+    p = detail_plan(rows, cin, cout, h, w, up)
+    return (p.bn, 'up' if up else 'plain', 'sliced' if p.S > 1 else 'whole')
+
+
+DETAIL_CLASSES = tuple((bn, u, s) for bn in (16, 64) for u in ('up', 'plain') for s in ('whole', 'sliced'))
 
 
 def batch_rows(B, n):

@@ -222,6 +222,32 @@ def test_lattice_cases_are_exact_in_every_precision(name):
         assert exact[22, 18] == {'nearer_wins': 3, 'nearer_wins_listed_first': 1}[name]
 
 
+def check_small_pair(name, S):
+    """One LATTICE mesh at one of the small sizes: safe by the rule of _exact_raster, and both precisions give the exact faces."""
+    verts, faces = C.LATTICE[name]
+    exact, unsafe = _exact_raster(verts, faces, S)
+    assert not unsafe, (name, S)
+    for dtype in (torch.float64, torch.float32):
+        assert np.array_equal(R.rasterize(verts[None], faces, S, dtype)[0][0].numpy(), exact), (name, S, dtype)
+    return exact
+
+
+@pytest.mark.parametrize('name,S', C.small_pairs(), ids=['%s_%d' % p for p in C.small_pairs()])
+def test_lattice_cases_are_exact_at_the_small_sizes(name, S):
+    exact = check_small_pair(name, S)
+    if S == 1:                                                              # the one centre is the origin
+        inside = {'covers_every_tile': 0, 'partly_outside': 0, 'reversed_winding': 0}
+        assert exact.shape == (1, 1) and int(exact[0, 0]) == inside.get(name, -1)
+    if name == 'quad_diagonal' and S == 17:
+        assert exact[8, 8] == -1 and exact[8, 9] == 0 and exact[9, 8] == 1  # on, right of and below the diagonal
+
+
+def test_the_dropped_small_pairings_cannot_be_proven():
+    """What SMALL_DROPPED leaves out is exactly what the rule calls unsafe: nothing is dropped for convenience."""
+    unsafe = {(name, S) for name in sorted(C.LATTICE) for S in C.SMALL_SIZES if _exact_raster(*C.LATTICE[name], S)[1]}
+    assert unsafe == set(C.SMALL_DROPPED)
+
+
 def test_lattice_grid_crosses_two_chunks_and_float32_agrees():
     verts, faces = C.lattice_grid()
     assert tuple(faces.shape) == (513, 3)
