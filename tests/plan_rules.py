@@ -3,7 +3,9 @@ which convs a forward pass launches at a given size, and into how many K slices 
 slices runs its epilogue in the finish kernel, one with S = 1 ("whole") in the conv kernel itself, so the number of finish launches
 of a pass is the number of launches with S > 1.  tests/test_cpu_e4e_taps.py and tests/test_cpu_s3fd.py pin the geometry to the C
 ABI and assert the coverage condition over the cases listed here; tests/test_gpu_s3fd_e4e_plans.py runs those cases and compares
-the profiler's launch counts with `e4e_counts` / `s3fd_counts`.  `detail_plan` is the same for the one layer kernel of csrc/detail.hip
+the profiler's launch counts with `e4e_counts` / `s3fd_counts`.  The e4e rules take the head count as an optional parameter (an
+encoder for the 512 or 1024 generator has 16 or 18 heads on any input side): tests/test_cpu_e4e_head_plans.py proves what the
+cases of E4E_HEADS_SMALL / E4E_HEADS_LARGE reach, tests/test_gpu_e4e_head_plans.py runs them.  `detail_plan` is the same for the one layer kernel of csrc/detail.hip
 (sgdfr_detail_upconv_f32): tests/test_cpu_render_seams.py proves what the cases of tests/render_seam_cases.py reach,
 tests/test_gpu_render_seams.py runs them."""
 from collections import OrderedDict, namedtuple
@@ -53,9 +55,19 @@ def e4e_units(R):
     return out
 
 
-def e4e_groups(R):
-    """(first head, one past the last, convs per head, side of the input map) of the three head groups."""
-    return ((0, 3, 4, R // 16), (3, 7, 5, R // 8), (7, e4e_style_count(R), 6, R // 4))
+E4E_MIN_HEADS, E4E_MAX_HEADS = 8, 18
+
+
+def e4e_heads(R, n=None):
+    """The head count: `n` (8..18, the encoder's 2 log2(image_resolution) - 2), by default the side's own."""
+    n = e4e_style_count(R) if n is None else n
+    assert E4E_MIN_HEADS <= n <= E4E_MAX_HEADS, n
+    return n
+
+
+def e4e_groups(R, n=None):
+    """(first head, one past the last, convs per head, side of the input map) of the three head groups of an encoder with n heads."""
+    return ((0, 3, 4, R // 16), (3, 7, 5, R // 8), (7, e4e_heads(R, n), 6, R // 4))
 
 
 def live_taps(side):
@@ -65,8 +77,9 @@ def live_taps(side):
     return [kh * 3 + kw for kh in range(3) for kw in range(3) if live[kh] and live[kw]]
 
 
-def e4e_launches(R):
-    """Every e4e_conv_kernel launch of one forward pass at resolution R, in launch order.  K counts the live taps only."""
+def e4e_launches(R, n=None):
+    """Every e4e_conv_kernel launch of one forward pass of an encoder with n heads at resolution R, in launch order.  K counts the
+    live taps only."""
     out = [Launch('stem', 'stem', 1, 64, R, R, 27)]
     for i, (cin, d, stride, h, ho, sc) in enumerate(e4e_units(R)):
         out.append(Launch('conv1', 'u%d.conv1' % i, 1, d, h, h, cin * 9))
@@ -75,7 +88,7 @@ def e4e_launches(R):
             out.append(Launch('shortcut', 'u%d.shortcut' % i, 1, d, ho, ho, cin))
     out.append(Launch('lateral', 'latlayer1', 1, 512, R // 8, R // 8, 256))
     out.append(Launch('lateral', 'latlayer2', 1, 512, R // 4, R // 4, 128))
-    for g, (lo, hi, depth, side) in enumerate(e4e_groups(R)):
+    for g, (lo, hi, depth, side) in enumerate(e4e_groups(R, n)):
         G = hi - lo
         for k in range(depth):
             so = (side - 1) // 2 + 1
@@ -88,17 +101,17 @@ def e4e_launches(R):
             else:
                 out.append(Launch('head_grouped' if G > 1 else 'head_single', 'g%d.k%d' % (g, k), G, 512, so, so, K))
             side = so
-    out.append(Launch('linear', 'linear', e4e_style_count(R), 512, 1, 1, 512))
+    out.append(Launch('linear', 'linear', e4e_heads(R, n), 512, 1, 1, 512))
     return out
 
 
-def e4e_plan(B, R):
-    return [(l, e4e_slices(B, l.G, l.N, l.Ho, l.Wo, l.K)) for l in e4e_launches(R)]
+def e4e_plan(B, R, n=None):
+    return [(l, e4e_slices(B, l.G, l.N, l.Ho, l.Wo, l.K)) for l in e4e_launches(R, n)]
 
 
-def e4e_counts(B, R):
+def e4e_counts(B, R, n=None):
     """(conv launches, finish launches) of one forward pass."""
-    plan = e4e_plan(B, R)
+    plan = e4e_plan(B, R, n)
     return len(plan), sum(S > 1 for _, S in plan)
 
 
@@ -114,6 +127,52 @@ E4E_EXCEPTIONS = OrderedDict([
 # runs the last head conv whole (7 heads x 8 channel tiles x ceil(B / 64) >= 192 only with 7 heads, i.e. R = 256, and B >= 193).
 E4E_SMALL = ((32, 2), (48, 3), (64, 3), (80, 2), (96, 2), (128, 3))
 E4E_LARGE = ((64, 96), (64, 192), (48, 192), (256, 194))
+# the GPU cases of tests/test_gpu_e4e_head_plans.py: encoders whose head count is not their side's own, (R, n, B).  Small batches of
+# distinct images (the encoders of tests/e4e_styles_cases.py; (32, 18, 2) and (80, 16, 3) are its cases d and e):
+#   (32, 16, 2)   9 fine heads on the smallest side; d is its 11-head twin
+#   (32, 18, 2)   case d: 11 fine heads, every head conv sliced
+#   (48, 18, 3)   fine maps 12 -> 6 -> 3 -> 2 -> 1 -> 1, pixel counts off the 64-pixel tile, 11 groups
+#   (64, 16, 3)   the first fine conv whole already at B = 3 (N = 4608 on 8 x 8 maps)
+#   (64, 14, 2)   7 fine heads: 56 R^2, the last count inside the unit buffer
+#   (80, 16, 3)   case e: first fine conv whole on 10 x 10 maps, the second in 3 slices
+#   (96, 18, 2)   first fine conv whole, N = 5632 on 12 x 12 maps; the second fine conv in 2 slices
+#   (128, 8, 2)   fewer heads than the side's own 12: one fine head, head_single on 16 x 16, 8 x 8, 4 x 4, 2 x 2 input maps
+E4E_HEADS_SMALL = ((32, 16, 2), (32, 18, 2), (48, 18, 3), (64, 16, 3), (64, 14, 2), (80, 16, 3), (96, 18, 2), (128, 8, 2))
+# batches of repeated rows, (R, n, B) -> (the launches the case is there for, the smallest B at which all of them run whole):
+#   (32, 18, 9)    head_first of the fine group whole (11 x 512 channels on 4 x 4 maps)
+#   (32, 18, 33)   head_grouped, G = 11, whole on 2 x 2 maps
+#   (32, 18, 65)   linear with 18 groups whole; the deeper fine convs drop to 2 slices
+#   (32, 18, 129)  every fine conv whole, head_last with 11 groups included: 41 finish launches of 70 convs
+#   (32, 16, 129)  the same with G = 9 and 16 linear groups
+#   (32, 18, 256)  the API's row limit: the 88 R^2 parked buffers at their largest row count for this side; nothing new runs whole
+#   (48, 18, 43)   grouped convs whole on 3 x 3 and 2 x 2 maps with partial pixel tiles (387 = 6 x 64 + 3 and 172 = 2 x 64 + 44
+#                  pixels).  They are whole from B = 33 on; 43 is the first B with a seventh pixel tile on the 3 x 3 maps
+#   (64, 16, 24)   G = 9 whole on 4 x 4 maps (from B = 9 on), 2 x 2 in 3 slices (B = 17 .. 32)
+#   (128, 8, 6)    the single fine head's first conv whole on 16 x 16 maps
+#   (256, 18, 3)   the real shape with more than one row: (70, 18) launches, three fine convs whole (the third, on 8 x 8 maps, from 3 rows on)
+E4E_HEADS_LARGE = OrderedDict([
+    ((32, 18, 9), (('g2.k0',), 9)),
+    ((32, 18, 33), (('g2.k1',), 33)),
+    ((32, 18, 65), (('linear',), 65)),
+    ((32, 18, 129), (('g2.k2', 'g2.k3', 'g2.k4', 'g2.k5'), 129)),
+    ((32, 16, 129), (('g2.k2', 'g2.k3', 'g2.k4', 'g2.k5'), 129)),
+    ((32, 18, 256), ((), 1)),
+    ((48, 18, 43), (('g2.k1', 'g2.k2'), 33)),
+    ((64, 16, 24), (('g2.k1',), 9)),
+    ((128, 8, 6), (('g2.k0',), 6)),
+    ((256, 18, 3), (('g2.k0', 'g2.k1', 'g2.k2'), 3)),
+])
+E4E_HEAD_CLASSES = ('head_first', 'head_grouped', 'head_last', 'linear')
+# (class, 'sliced' or 'whole', groups) that the head-count cases leave to another list, each with its reason
+E4E_HEADS_EXCEPTIONS = OrderedDict([
+    (('head_single', 'whole', 1), 'a deeper conv of a single fine head runs whole from 24 rows on at R = 128 (8 x 8 maps), at a cost '
+                                  'of a 128 x 128 trunk on 24 rows; (48, 192) of E4E_LARGE runs this kernel path whole and stays the witness'),
+])
+
+
+def e4e_head_key(l, S):
+    """(class, 'sliced' | 'whole', groups in the launch); for head_first the heads whose channels the one conv holds, N / 512."""
+    return (l.cls, 'sliced' if S > 1 else 'whole', l.N // 512 if l.cls == 'head_first' else l.G)
 
 
 def coverage(plans, classes):
